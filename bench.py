@@ -9,18 +9,25 @@ solves the contiguous slice [r B/N, (r+1) B/N) of it, resident in its HBM.  One 
 timed region), ``"scaling": "strong"``.
 
     python bench.py [--gpus N --steps K --warmup W --config 3|2|1 --batch B]
+                    [--dump-outputs DIR] [--full]
 
 ``--gpus N`` (N > 1) without a torch.distributed environment re-launches this script under
 ``torch.distributed.run`` with N ranks (before anything touches the GPU); under an existing
 launcher WORLD_SIZE must equal N.
 
-Also on the line:
+A plain run sets up, warms up, times the K steps and prints the line: the headline with the
+rooflines and acceptance statistics of the timed steps themselves.  ``--dump-outputs DIR`` also
+writes what the last timed step returned (w, status, iters) as ``DIR/<name>.npy``; the inputs
+are seeded, so two builds can be compared output for output.
+
+With ``--full``, also on the line (each takes runs of its own):
   * ``scatter_gather`` (N > 1): the same global batch owned by rank 0 -- one RCCL scatter of
     the input stacks, the solve, one RCCL gather of w per step (cmpc/dist.py);
   * ``weak``: every rank solves the whole 65,536-instance batch (per-GPU work fixed);
   * ``configs`` (N = 1): BASELINE configs 1 (B = 256) and 2 (B = 4,096), plus configs 1 and 2
     at B = 65,536, each timed the same way with its own roofline;
-  * ``roofline``: the dominant solve kernel (of the three, cmpc_host.hip) priced against HBM:
+  * ``roofline`` (on every line: it is measured on the timed steps): the dominant solve kernel
+    (of the three, cmpc_host.hip) priced against HBM:
     12,264 algorithmic bytes per solve (inputs 10,720 + outputs 1,544) x the solves it
     processed / its average HIP-event duration on its own stream; ``traffic`` = the PMC HBM
     bytes per launch from profiles/;
@@ -126,8 +133,15 @@ def parse(argv=None):
                     help="timed closed-loop MPC ticks (config 4 shape, SRB plant); 0 = skip")
     ap.add_argument("--api-ticks", type=int, default=20,
                     help="config 0: ticks of one robot through the CentroidalMPC drop-in; 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (sub-configs, scatter/gather "
+                         "and weak variants, shard rehearsal, the 8(f) objects, CPU baseline); "
+                         "without it the options of those objects are ignored")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
     ap.add_argument("--aux", type=int, default=1,
-                    help="0 = headline only (profiling runs): skips every other object")
+                    help="with --full: 0 = headline only again (plus the scatter / weak variants "
+                         "whose steps are given explicitly)")
     ap.add_argument("--seed-offset", type=int, default=0,
                     help="added to the workload seed (experiments: average over batches)")
     ap.add_argument("--param", action="append",
@@ -143,6 +157,10 @@ def parse(argv=None):
     ap.add_argument("--lib", type=str, default=None,
                     help="alternative build of libcmpc.so (A/B experiments)")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:   # a plain run: the headline's own steps and nothing else
+        a.aux = a.scatter_steps = a.weak_steps = 0
     if not a.aux:
         a.cpu_seconds = 0
         a.sub_configs = a.dynamics_steps = a.warm_steps = a.tick_steps = 0
@@ -303,6 +321,34 @@ def kernel_roofline(plan, B_shard, bins, contact, iters, ms, calls, traffic=None
     return roof, comp, crit
 
 
+DUMP_W_ROWS = 16384   # rows of w written by --dump-outputs: 16,384 x 384 x 4 B = 24 MiB
+
+
+def dump_rows(B, cap=DUMP_W_ROWS):
+    """Rows of a B-row output that --dump-outputs writes: all of them up to `cap`, else a fixed
+    seeded sample of `cap` rows in ascending order (the same for every run and build)."""
+    if B <= cap:
+        return np.arange(B)
+    return np.sort(np.random.default_rng(20240607).choice(B, cap, replace=False))
+
+
+def dump_outputs(dirname, w, status, iters, rank=0, world=1):
+    """Write what the last timed step returned on this rank as float32 DIR/<name>.npy: `w` (the
+    rows dump_rows picks, with their indices in `w_rows`), `status` and `iters` of every
+    instance.  With more than one rank the names carry `_rank<r>` and the row cap is split."""
+    out = Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    rows = dump_rows(w.shape[0], max(DUMP_W_ROWS // world, 1))
+    sfx = f"_rank{rank}" if world > 1 else ""
+    if isinstance(w, np.ndarray):
+        wr = w[rows]
+    else:   # a device tensor: gather the rows there, copy only them
+        import torch
+        wr = w[torch.as_tensor(rows, device=w.device)].cpu().numpy()
+    for name, a in (("w", wr), ("w_rows", rows), ("status", status), ("iters", iters)):
+        np.save(out / f"{name}{sfx}.npy", np.ascontiguousarray(a, dtype=np.float32))
+
+
 def load_json(path):
     if path and Path(path).exists():
         try:
@@ -407,6 +453,8 @@ def main(argv=None):
     solved = reduce_sum_int(int((st == 1).sum().item()))
     status = st.cpu().numpy()
     iters = it.cpu().numpy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, w, status, iters, rank, world)
     value = GB * args.steps / elapsed
     bins = bins_of(shard["contact"])
     traffic_j = load_json(args.traffic_json)

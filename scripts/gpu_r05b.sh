@@ -17,7 +17,7 @@ grep -E "above 1e-4|^cfg" gpurun_out/survey_r04_cpu.log
 timeout -k 10 300 python -u tests/certify_sample.py gpu > gpurun_out/survey_gpu.log 2>&1 || { tail -5 gpurun_out/survey_gpu.log; exit 1; }
 timeout -k 10 900 python -u tests/certify_sample.py cpu > gpurun_out/survey_cpu.log 2>&1 || { tail -5 gpurun_out/survey_cpu.log; exit 1; }
 grep -E "above 1e-4|^cfg|status" gpurun_out/survey_cpu.log
-W="--cpu-seconds 0 --sub-configs 0 --dynamics-steps 0 --tick-steps 0 --leg-steps 0 --loop-steps 0 --api-ticks 0 --steps 5"
+W="--full --cpu-seconds 0 --sub-configs 0 --dynamics-steps 0 --tick-steps 0 --leg-steps 0 --loop-steps 0 --api-ticks 0 --steps 5"
 for v in "$L/libcmpc_r04.so" "$L/libcmpc.so" "$L/libcmpc.so@CMPC_TOP_GRID=64"; do
   lib=${v%%@*}; envs=""; [ "$v" != "$lib" ] && envs=${v#*@}
   env CMPC_ALLOW_ABI4=1 $envs timeout -k 10 300 python bench.py $W --lib $lib > gpurun_out/warm_$(basename $lib .so)${envs:+_top}.json 2>/dev/null || { echo "bench failed $v"; exit 1; }

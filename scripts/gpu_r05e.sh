@@ -11,13 +11,14 @@ rc=$?; tail -1 gpurun_out/gpu_tests.log; [ $rc -eq 0 ] || { grep -E "^FAILED|Err
 timeout -k 10 300 python -u tests/certify_sample.py gpu > gpurun_out/survey_gpu.log 2>&1 || { tail -5 gpurun_out/survey_gpu.log; exit 1; }
 timeout -k 10 600 python -u tests/certify_sample.py cpu > gpurun_out/survey_cpu.log 2>&1 || { tail -5 gpurun_out/survey_cpu.log; exit 1; }
 grep -E "above 1e-4|^cfg" gpurun_out/survey_cpu.log
-timeout -k 10 400 python -u bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err || { tail -5 gpurun_out/bench_default.err; exit 1; }
-LOOP="--sub-configs 0 --dynamics-steps 0 --tick-steps 0 --leg-steps 0 --api-ticks 0 --cpu-seconds 1"
-CMPC_TEAM_OCC=1 timeout -k 10 300 python -u bench.py $LOOP > gpurun_out/bench_occ1.json 2> gpurun_out/bench_occ1.err || { tail -5 gpurun_out/bench_occ1.err; exit 1; }
+export BENCH_DIR=${BENCH_DIR:-$TMPDIR}
+timeout -k 10 600 python -u bench.py --full > $BENCH_DIR/bench_default.json 2> $BENCH_DIR/bench_default.err || { tail -5 $BENCH_DIR/bench_default.err; exit 1; }
+LOOP="--full --sub-configs 0 --dynamics-steps 0 --tick-steps 0 --leg-steps 0 --api-ticks 0 --cpu-seconds 1"
+CMPC_TEAM_OCC=1 timeout -k 10 300 python -u bench.py $LOOP > $BENCH_DIR/bench_occ1.json 2> $BENCH_DIR/bench_occ1.err || { tail -5 $BENCH_DIR/bench_occ1.err; exit 1; }
 python - <<'EOF'
-import json
+import json, os
 for f in ("bench_default", "bench_occ1"):
-    a = json.loads(open(f"gpurun_out/{f}.json").read().strip().splitlines()[-1])
+    a = json.loads(open(os.path.join(os.environ["BENCH_DIR"], f + ".json")).read().strip().splitlines()[-1])
     w = a.get("warm_start", {}); cl = a.get("closed_loop", {}).get("robots_1024", {})
     print(f, "value %.0f ms %.3f" % (a["value"], a["ms_per_step"]),
           "warm itmax %s cold itmax %s warm p999 %s cold p999 %s" % (w.get("iters_max_warm"), w.get("iters_max_cold"), w.get("iters_p999_warm"), w.get("iters_p999_cold")),

@@ -21,6 +21,7 @@ for c in 1 2; do
 done
 TESTS=0 R=2 CASES="3:65536 2:4096 1:256 2:65536" bash scripts/gpu_ab.sh $L/libcmpc.so $L/libcmpc_inv.so || exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/span -o run --output-format csv -- python bench.py --aux 0 --config 1 --batch 65536 --steps 5 --warmup 1 > gpurun_out/span.log 2>&1 || { tail -5 gpurun_out/span.log; exit 1; }
-timeout -k 10 400 python -u bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err || { tail -5 gpurun_out/bench_default.err; exit 1; }
-tail -c 600 gpurun_out/bench_default.json
+BENCH_DIR=${BENCH_DIR:-$TMPDIR}
+timeout -k 10 600 python -u bench.py --full > $BENCH_DIR/bench_default.json 2> $BENCH_DIR/bench_default.err || { tail -5 $BENCH_DIR/bench_default.err; exit 1; }
+tail -c 600 $BENCH_DIR/bench_default.json
 echo done

@@ -21,5 +21,5 @@ done
 timeout -k 10 300 python -u tests/certify_sample.py gpu > gpurun_out/survey_gpu.log 2>&1 || { tail -5 gpurun_out/survey_gpu.log; exit 1; }
 timeout -k 10 600 python -u tests/certify_sample.py cpu > gpurun_out/survey_cpu.log 2>&1 || { tail -5 gpurun_out/survey_cpu.log; exit 1; }
 grep -E "above 1e-4" gpurun_out/survey_cpu.log
-python -c "import json;a=json.loads(open('gpurun_out/bench_full.json').read().strip().splitlines()[-1]);print('value %.0f ms %.3f roofline %.4f'%(a['value'],a['ms_per_step'],a['roofline']['frac']))"
+python -c "import json;a=json.loads(open('${OUT:-profile_out}/bench_full.json').read().strip().splitlines()[-1]);print('value %.0f ms %.3f roofline %.4f'%(a['value'],a['ms_per_step'],a['roofline']['frac']))"
 echo done

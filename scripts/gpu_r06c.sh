@@ -22,7 +22,7 @@ rm -f $O/*.npz
 timeout -k 10 300 python -u tools/straggler_speed.py profiles/r06b_diag/diag_cfg3.npz 8 > $O/straggler_speed.txt 2>&1 || { tail -5 $O/straggler_speed.txt; exit 1; }
 cat $O/straggler_speed.txt
 TESTS=0 R=2 CASES="3:65536 2:4096" bash scripts/gpu_ab.sh $L/libcmpc_r5.so $L/libcmpc_prodg.so $L/libcmpc.so 2>&1 | grep -v "^done" || exit 1
-timeout -k 10 600 python -u bench.py > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 python -c "
 import json; a=json.load(open('$O/bench.json'))
 print('bench', a['value'], a['ms_per_step'], a['status_counts'], a['acceptance_per_step'], a['roofline']['frac'])

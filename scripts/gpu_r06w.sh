@@ -6,7 +6,7 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 L=convex-mpc-unitree-go2_amd/cmpc/lib; O=gpurun_out/r06w; mkdir -p $O
 for v in libcmpc libcmpc_warm4; do
-  timeout -k 10 400 python bench.py --sub-configs 0 --cpu-seconds 0 --lib $L/$v.so > $O/bench_$v.json 2> $O/bench_$v.err || { tail -5 $O/bench_$v.err; exit 1; }
+  timeout -k 10 400 python bench.py --full --sub-configs 0 --cpu-seconds 0 --lib $L/$v.so > $O/bench_$v.json 2> $O/bench_$v.err || { tail -5 $O/bench_$v.err; exit 1; }
   python -c "import json;a=json.load(open('$O/bench_$v.json'));w=a['warm_start'];c=a['closed_loop'];print('$v cold %.3f ms, warm %.2f M/s (x%.2f), loop65536 %.3f/%.3f, loop1024 %.3f'%(a['ms_per_step'],w['solves_per_s_warm']/1e6,w['speedup'],c['robots_65536']['ms_per_tick_eager'],c['robots_65536']['ms_per_tick_graph'],c['robots_1024']['ms_per_tick_graph']))"
 done
 cp $L/libcmpc_warm4.so $L/libcmpc.so

@@ -12,7 +12,7 @@ case $rc in 0|1) ;; *) echo "tests aborted ($rc)"; exit 1;; esac
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 || { tail -5 gpurun_out/smoke.log; exit 1; }
 tail -1 gpurun_out/smoke.log
 FULL=1 bash scripts/gpu_profile.sh > gpurun_out/profile_run.log 2>&1 || { tail -5 gpurun_out/profile_run.log; exit 1; }
-python -c "import json;a=json.loads(open('gpurun_out/bench_full.json').read().strip().splitlines()[-1]);c=a['closed_loop'];print('value %.0f ms %.3f roofline %.4f acceptance %s loop65536 eager %.3f graph %.3f loop1024 graph %.3f'%(a['value'],a['ms_per_step'],a['roofline']['frac'],a['acceptance_per_step'],c['robots_65536']['ms_per_tick_eager'],c['robots_65536']['ms_per_tick_graph'],c['robots_1024']['ms_per_tick_graph']))"
+python -c "import json;a=json.loads(open('${OUT:-profile_out}/bench_full.json').read().strip().splitlines()[-1]);c=a['closed_loop'];print('value %.0f ms %.3f roofline %.4f acceptance %s loop65536 eager %.3f graph %.3f loop1024 graph %.3f'%(a['value'],a['ms_per_step'],a['roofline']['frac'],a['acceptance_per_step'],c['robots_65536']['ms_per_tick_eager'],c['robots_65536']['ms_per_tick_graph'],c['robots_1024']['ms_per_tick_graph']))"
 timeout -k 10 300 python -u tools/shard_times.py "" 5 > gpurun_out/shard_rehearsal.log 2>&1 || { tail -5 gpurun_out/shard_rehearsal.log; exit 1; }
 grep N= gpurun_out/shard_rehearsal.log
 for B in 65536 1024; do

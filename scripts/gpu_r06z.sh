@@ -13,7 +13,7 @@ case $rc in 0|1) ;; *) echo "tests aborted ($rc)"; exit 1;; esac
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 || { tail -5 gpurun_out/smoke.log; exit 1; }
 tail -1 gpurun_out/smoke.log
 FULL=1 bash scripts/gpu_profile.sh > gpurun_out/profile_run.log 2>&1 || { tail -5 gpurun_out/profile_run.log; exit 1; }
-python -c "import json;a=json.loads(open('gpurun_out/bench_full.json').read().strip().splitlines()[-1]);print('value %.0f ms %.3f roofline %.4f acceptance %s'%(a['value'],a['ms_per_step'],a['roofline']['frac'],a['acceptance_per_step']))"
+python -c "import json;a=json.loads(open('${OUT:-profile_out}/bench_full.json').read().strip().splitlines()[-1]);print('value %.0f ms %.3f roofline %.4f acceptance %s'%(a['value'],a['ms_per_step'],a['roofline']['frac'],a['acceptance_per_step']))"
 timeout -k 10 300 rocprofv3 --kernel-trace -d gpurun_out/prof_cfg1 -o run --output-format csv -- python bench.py --aux 0 --config 1 --batch 65536 --sub-configs 0 --cpu-seconds 0 --steps 5 --warmup 1 > gpurun_out/prof_cfg1.log 2>&1 || { tail -5 gpurun_out/prof_cfg1.log; exit 1; }
 timeout -k 10 300 python -u tools/shard_times.py "" 5 > gpurun_out/shard_rehearsal.log 2>&1 || { tail -5 gpurun_out/shard_rehearsal.log; exit 1; }
 grep N= gpurun_out/shard_rehearsal.log

@@ -22,6 +22,49 @@ def test_counters_lookup_ignores_template_flag():
     assert bench._counters_of(None, "solve_group_kernel<128, 96>") is None
 
 
+def test_plain_run_is_headline_only_and_full_restores_the_rest():
+    """Without --full every object beside the headline is off, whatever its own option says;
+    --full brings back the defaults (and --full --aux 0 is headline only again)."""
+    extra = ("sub_configs", "dynamics_steps", "warm_steps", "tick_steps", "leg_steps",
+             "loop_steps", "api_ticks", "cpu_seconds", "scatter_steps", "weak_steps", "aux")
+    for argv in (["--gpus", "1", "--steps", "7", "--warmup", "2"],
+                 ["--steps", "7", "--warmup", "2", "--loop-steps", "24", "--weak-steps", "5"]):
+        a = bench.parse(argv)
+        assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+        assert all(getattr(a, k) == 0 for k in extra), vars(a)
+    f = bench.parse(["--full", "--steps", "7"])
+    assert f.full and f.aux == 1 and f.sub_configs == 1 and f.cpu_seconds == 15.0
+    assert (f.dynamics_steps, f.warm_steps, f.tick_steps, f.leg_steps) == (5, 5, 5, 5)
+    assert (f.loop_steps, f.api_ticks, f.scatter_steps, f.weak_steps) == (24, 20, 7, 7)
+    g = bench.parse(["--full", "--aux", "0", "--weak-steps", "3"])
+    assert g.sub_configs == g.loop_steps == g.cpu_seconds == g.scatter_steps == 0
+    assert g.weak_steps == 3
+
+
+def test_dump_outputs_writes_float32_sample(tmp_path):
+    """--dump-outputs: w rows are a fixed ascending sample above the cap (all rows below it),
+    every array is float32 .npy, and two dumps of the same outputs are identical."""
+    import numpy as np
+    cap = bench.DUMP_W_ROWS
+    assert cap * 384 * 4 + 3 * 65536 * 4 <= 64 * 2 ** 20
+    assert bench.dump_rows(100).tolist() == list(range(100))
+    rows = bench.dump_rows(cap + 1000)
+    assert len(rows) == cap and np.all(np.diff(rows) > 0) and rows[-1] < cap + 1000
+    assert np.array_equal(rows, bench.dump_rows(cap + 1000))
+    B = 300
+    w = np.arange(B * 384, dtype=np.float32).reshape(B, 384)
+    st, it = np.ones(B, np.int32), np.arange(B, dtype=np.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, w, st, it)
+    got = {p.stem: np.load(p) for p in sorted((tmp_path / "a").glob("*.npy"))}
+    assert sorted(got) == ["iters", "status", "w", "w_rows"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert np.array_equal(got["w"], w) and np.array_equal(got["iters"], it)
+    assert all(np.array_equal(v, np.load(tmp_path / "b" / f"{k}.npy")) for k, v in got.items())
+    bench.dump_outputs(tmp_path / "r", w, st, it, rank=1, world=64)   # cap split over the ranks
+    assert np.load(tmp_path / "r" / "w_rank1.npy").shape == (cap // 64, 384)
+
+
 class _StubPlan:
     def __init__(self, names):
         self.names = names
