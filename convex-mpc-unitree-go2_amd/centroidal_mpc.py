@@ -119,7 +119,10 @@ class CentroidalMPC:
         print(f"  vars: {self.nvars:d} | constr: {nA_rows:d} | horizon N = {N}")
         print("[QP Init] ✓ Initialization complete.\n")
 
-    def solve_QP(self, go2, traj, verbose: bool = False):
+    def solve_QP(self, go2, traj, verbose: bool = False, *, mu=None, fz_min=None):
+        """The reference's solve_QP.  ``mu`` / ``fz_min`` (keyword only, beyond the reference):
+        this tick's friction coefficient and stance normal-force floor for the robot; None
+        keeps the module constants MU / FZ_MIN."""
         torch = self._torch
         t0 = time.perf_counter()
         N = self.N
@@ -143,6 +146,9 @@ class CentroidalMPC:
             kw["w_init"] = self._out[0]
         if self._warm and OPTS["warm_start_dual"]:
             kw["lam_init"] = self._lam
+        for name, v in (("mu", mu), ("fz_min", fz_min)):
+            if v is not None:
+                kw[name] = torch.full((1,), float(v), dtype=torch.float32, device=self.plan.device)
         w, st, it = self.plan.solve(b["Ad"], b["Bd"], b["gd"], b["x0"], b["xref"], b["contact"],
                                     out=self._out, lam_out=self._lam, **kw)
         self._warm = True

@@ -5,7 +5,8 @@ ticks it calls ``traj.generate_traj`` and ``mpc.solve_QP`` (warm-started) and ho
 until the next MPC tick; MuJoCo integrates the robot.  Here one call of :meth:`ClosedLoop.tick`
 does that for B robots with no host round trip:
 
-  cmpc_generate_traj -> cmpc_build_dynamics -> cmpc_solve_warm -> cmpc_srb_step (nsub substeps)
+  cmpc_generate_traj -> cmpc_build_dynamics -> cmpc_solve_warm (cmpc_solve_io_run with
+  per-robot terrain) -> cmpc_srb_step (nsub substeps)
 
 MuJoCo and the Go2 model are absent from this image, so the plant is ``cmpc_srb_step``'s
 single-rigid-body stand-in (include/cmpc.h) and the robot quantities Pinocchio would supply are
@@ -35,11 +36,18 @@ def rot_zyx(rpy: torch.Tensor) -> torch.Tensor:
 
 
 class ClosedLoop:
-    """B robots walking under batched MPC (test_MPC.py's loop shape, MPC_DT = gait period / N)."""
+    """B robots walking under batched MPC (test_MPC.py's loop shape, MPC_DT = gait period / N).
+
+    ``mu`` / ``fz_min``: per-robot friction coefficient and stance normal-force floor, (B,)
+    values (None: the plan's constants).  The loop keeps them as the device tensors ``self.mu``
+    / ``self.fz_min`` and passes them to every solve by pointer: writing new values into them in
+    place (``loop.mu.copy_(...)``, a terrain estimator's output) takes effect at the next tick,
+    a replay of the captured graph included.  They bound the forces the MPC plans; the
+    single-rigid-body plant has no friction model and applies the planned forces as they are."""
 
     def __init__(self, B: int, plan: Optional[Plan] = None, gait_hz: float = synth.GAIT_HZ,
                  duty: float = synth.GAIT_DUTY, offsets=synth.TROT_OFFSETS, nsub: int = 20,
-                 seed: int = 0, device="cuda", shift_warm: bool = True):
+                 seed: int = 0, device="cuda", shift_warm: bool = True, mu=None, fz_min=None):
         self.plan = plan or Plan(SolverParams(max_batch=B))
         self.B, self.N = B, self.plan.params.N
         dev = torch.device(device)
@@ -84,6 +92,10 @@ class ClosedLoop:
         self.I_world = torch.empty((B, 3, 3), dtype=f32, device=dev)
         self.w_init = torch.zeros_like(self.w)
         self.y_init = torch.zeros_like(self.y)
+        self.mu, self.fz_min = (
+            None if v is None else
+            torch.as_tensor(v, dtype=f32).expand(B).contiguous().to(dev, copy=True)
+            for v in (mu, fz_min))
         self.shift_warm = shift_warm
         self.warm = False
         self.graph = None
@@ -117,7 +129,8 @@ class ClosedLoop:
         else:
             kw = dict(w_init=self.w, y_init=self.y) if warm else {}
         p.solve(self.Ad, self.Bd, self.gd, self.x, self.xref, self.ct,
-                out=(self.w, self.status, self.iters), stream=stream, y_out=self.y, **kw)
+                out=(self.w, self.status, self.iters), stream=stream, y_out=self.y,
+                mu=self.mu, fz_min=self.fz_min, **kw)
         sp = ctypes.c_void_p(stream.cuda_stream)
         P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
         force = self.w[:, 12 * N:]                        # U[:, 0] rows (test_MPC.py:196)

@@ -12,6 +12,7 @@ import torch
 import torch.distributed as dist
 
 FIELDS = ("Ad", "Bd", "gd", "x0", "xref", "contact")
+TERRAIN = ("mu", "fz_min")    # optional (B,) stacks: per-instance terrain (Plan.solve)
 
 
 def shard_bounds(B: int, rank: int, world: int):
@@ -24,7 +25,7 @@ def shard_bounds(B: int, rank: int, world: int):
 def shard_batch(batch: dict, rank: int, world: int) -> dict:
     B = batch["Ad"].shape[0]
     lo, hi = shard_bounds(B, rank, world)
-    return {k: batch[k][lo:hi] for k in FIELDS}
+    return {k: batch[k][lo:hi] for k in FIELDS + tuple(t for t in TERRAIN if t in batch)}
 
 
 def _pad_chunks(t: torch.Tensor, world: int):
@@ -40,16 +41,18 @@ def _pad_chunks(t: torch.Tensor, world: int):
     return chunks, per
 
 
-def scatter_batch(batch: dict | None, B: int, N: int, device, group=None) -> dict:
+def scatter_batch(batch: dict | None, B: int, N: int, device, group=None,
+                  terrain: bool = False) -> dict:
     """Rank 0 holds `batch` (tensors on `device`); every rank receives its shard.  All ranks
-    pass the global B and horizon N."""
+    pass the global B and horizon N.  terrain=True (on every rank: each stack is one
+    collective) also scatters the (B,) fp32 stacks `mu` and `fz_min` of rank 0's batch."""
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     lo, hi = shard_bounds(B, rank, world)
     per = (B + world - 1) // world
     shapes = {"Ad": (12, 12), "Bd": (N, 12, 12), "gd": (12,), "x0": (12,), "xref": (N, 12),
-              "contact": (4, N)}
+              "contact": (4, N), "mu": (), "fz_min": ()}
     out = {}
-    for k in FIELDS:
+    for k in FIELDS + (TERRAIN if terrain else ()):
         dt = torch.uint8 if k == "contact" else torch.float32
         recv = torch.empty((per,) + shapes[k], dtype=dt, device=device)
         if rank == 0:

@@ -188,7 +188,7 @@ class Plan:
         return list(ms)[:k], list(calls)[:k]
 
     def solve(self, Ad, Bd, gd, x0, xref, contact, out=None, stream=None, w_init=None,
-              y_init=None, y_out=None, lam_init=None, lam_out=None):
+              y_init=None, y_out=None, lam_init=None, lam_out=None, mu=None, fz_min=None):
         """Solve B instances; all inputs are device tensors (layouts: include/cmpc.h).
 
         Returns (w (B, 24N) fp32, status (B,) int32, iters (B,) int32).  Asynchronous on
@@ -203,7 +203,14 @@ class Plan:
         ``lam_init`` (B, 52N) warm duals [lam_x | lam_a] in CasADi's layout and convention,
         ``lam_out`` (B, 52N) the multipliers of the returned point (``lam_out=True``
         allocates it; the return is then (w, status, iters, lam)).  Not combinable with
-        y_init / y_out."""
+        y_init / y_out.
+
+        Per-instance terrain (cmpc_solve_io_run): ``mu`` (B,) the friction coefficient and
+        ``fz_min`` (B,) the stance normal-force floor of each instance, fp32 device tensors;
+        None takes the plan's constant.  They combine with every option above.  The kernels
+        read them when they run, so a captured graph sees values written in place since.  An
+        instance whose entry is invalid (mu not finite or <= 0, fz_min not finite) returns
+        status -10 with zero forces; the others are unaffected."""
         N = self.params.N
         B = Ad.shape[0]
         f32 = torch.float32
@@ -229,6 +236,9 @@ class Plan:
         if stream is None:
             stream = torch.cuda.current_stream(Ad.device)
         sp = ctypes.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else stream)
+        if mu is not None or fz_min is not None:
+            return self._solve_io(B, (Ad, Bd, gd, x0, xref, contact), (w, status, iters), sp,
+                                  w_init, y_init, y_out, lam_init, lam_out, mu, fz_min)
         if lam_init is not None or lam_out is not None:
             if y_init is not None or y_out is not None:
                 raise ValueError("lam_init/lam_out (reference layout) and y_init/y_out "
@@ -277,6 +287,41 @@ class Plan:
         if ret_y:
             return w, status, iters, y_out
         return w, status, iters
+
+    def _solve_io(self, B, inputs, outs, sp, w_init, y_init, y_out, lam_init, lam_out, mu, fz_min):
+        """solve() with per-instance mu / fz_min: the struct entry cmpc_solve_io_run."""
+        if not hasattr(self.lib, "cmpc_solve_io_run"):
+            raise CmpcError("cmpc: this libcmpc.so has no cmpc_solve_io_run: per-instance mu / "
+                            "fz_min need a library built from sources that declare it")
+        if (lam_init is not None or lam_out is not None) and (y_init is not None or y_out is not None):
+            raise ValueError("lam_init/lam_out (reference layout) and y_init/y_out "
+                             "(cmpc layout) are exclusive")
+        N = self.params.N
+        f32 = torch.float32
+        dev = inputs[0].device
+        ret_y, ret_l = y_out is True, lam_out is True
+        if ret_y:
+            y_out = torch.empty((B, 12 * N), dtype=f32, device=dev)
+        if ret_l:
+            lam_out = torch.empty((B, 52 * N), dtype=f32, device=dev)
+        opt = dict(mu=(mu, (B,)), fz_min=(fz_min, (B,)), w_init=(w_init, (B, 24 * N)),
+                   y_init=(y_init, (B, 12 * N)), lam_init=(lam_init, (B, 52 * N)),
+                   y_out=(y_out, (B, 12 * N)), lam_out=(lam_out, (B, 52 * N)))
+        io = _lib.CSolveIO()
+        io.size = ctypes.sizeof(_lib.CSolveIO)
+        for name, (t, shape) in opt.items():
+            if t is not None:
+                _dev_tensor(t, name, f32, shape)
+                self._same_device(t)
+                setattr(io, name, t.data_ptr())
+        for name, t in zip(("Ad", "Bd", "gd", "x0", "xref", "contact"), inputs):
+            setattr(io, name, t.data_ptr())
+        for name, t in zip(("w_out", "status", "iters"), outs):
+            setattr(io, name, t.data_ptr())
+        with torch.cuda.device(dev):
+            rc = self.lib.cmpc_solve_io_run(self._h, ctypes.c_int64(B), ctypes.byref(io), sp)
+        _check(self.lib, rc, "cmpc_solve_io_run")
+        return outs + ((y_out,) if ret_y else ()) + ((lam_out,) if ret_l else ())
 
     def build_dynamics(self, mass, inertia, r_feet, xref, dt, out=None, stream=None):
         """Discrete dynamics (Ad, Bd, gd) of B robots on the device -- the reference's
@@ -416,6 +461,9 @@ def to_device_batch(batch: dict, device="cuda") -> dict:
     for k in ("Ad", "Bd", "gd", "x0", "xref"):
         out[k] = torch.as_tensor(batch[k], dtype=torch.float32).contiguous().to(device)
     out["contact"] = torch.as_tensor(batch["contact"], dtype=torch.uint8).contiguous().to(device)
+    for k in ("mu", "fz_min"):      # per-instance terrain (synth.make_terrain), when present
+        if batch.get(k) is not None:
+            out[k] = torch.as_tensor(batch[k], dtype=torch.float32).contiguous().to(device)
     return out
 
 
@@ -423,6 +471,7 @@ def solve_batch(batch: dict, params: Optional[SolverParams] = None, plan: Option
     """Convenience: numpy batch in, (w, status, iters) numpy out (synchronises)."""
     plan = plan or Plan(params)
     d = to_device_batch(batch, plan.device)
-    w, st, it = plan.solve(d["Ad"], d["Bd"], d["gd"], d["x0"], d["xref"], d["contact"])
+    w, st, it = plan.solve(d["Ad"], d["Bd"], d["gd"], d["x0"], d["xref"], d["contact"],
+                           mu=d.get("mu"), fz_min=d.get("fz_min"))
     torch.cuda.synchronize(plan.device)
     return w.cpu().numpy(), st.cpu().numpy(), it.cpu().numpy()

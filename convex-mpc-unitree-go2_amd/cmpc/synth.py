@@ -189,6 +189,25 @@ def make_tick_inputs(B: int, seed: int, mixed: bool = False, N: int = N_HORIZON,
                 hip=f32(HIP_OFFSETS), m=m, I_world=I_world, dt=period / N, N=N)
 
 
+def make_terrain(B: int, seed: int, mu=(0.2, 1.0), fz_min=(0.0, 20.0)) -> dict:
+    """Per-instance terrain for a batch of ``B``: friction coefficient ``mu`` ~ U(mu) and stance
+    normal-force floor ``fz_min`` ~ U(fz_min), the ``mu`` / ``fz_min`` arrays of
+    ``cmpc_solve_io`` (include/cmpc.h).  float64 arrays of fp32-representable values inside the
+    closed ranges.  Its generator is its own: the draws of :func:`make_batch` do not depend on
+    it."""
+    rng = np.random.default_rng(seed)
+
+    def draw(lo, hi):
+        lo32, hi32 = np.float32(lo), np.float32(hi)
+        if lo32 < lo:
+            lo32 = np.nextafter(lo32, np.float32(np.inf))
+        if hi32 > hi:
+            hi32 = np.nextafter(hi32, np.float32(-np.inf))
+        v = rng.uniform(lo, hi, B).astype(np.float32)
+        return np.clip(v, lo32, hi32).astype(np.float64)
+    return dict(mu=draw(*mu), fz_min=draw(*fz_min))
+
+
 CONFIGS = {
     0: dict(B=1, seed=0, mixed=False),
     1: dict(B=256, seed=1, mixed=False),

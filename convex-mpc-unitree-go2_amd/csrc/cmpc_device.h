@@ -35,6 +35,8 @@ struct Inputs {
   const float* w_init;  // nullable: primal warm start, cmpc_solve_warm's w layout
   const float* y_init;  // nullable: dual warm start [B][12N] (force layout)
   const float* lam_init;  // nullable: the reference's warm duals [B][52N] = [lam_x | lam_a]
+  const float* mu;      // nullable: per-instance friction coefficient [B] (NULL: KParams::mu)
+  const float* fz_min;  // nullable: per-instance stance fz floor [B] (NULL: KParams::fz_min)
 };
 struct Outputs {
   float* w;

@@ -1,5 +1,6 @@
 // cmpc_host.hip -- C-ABI (include/cmpc.h): plan management and kernel launches.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdlib.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -288,45 +289,66 @@ int cmpc_plan_create(const cmpc_params* p, cmpc_plan** out) {
 static int solve_impl(cmpc_plan* pl, int64_t B, const cmpc::Inputs& in, const cmpc::Outputs& out,
                       void* stream);
 
+// the argument checks every solve entry shares (`what` names the entry in the message)
+static int solve_checked(cmpc_plan* pl, int64_t B, const cmpc::Inputs& in, cmpc::Outputs out,
+                         void* stream, const char* what) {
+  const std::string w(what);
+  if (!pl) return fail(CMPC_E_INVALID, w + ": null plan");
+  if (B < 0) return fail(CMPC_E_INVALID, w + ": negative batch");
+  if (B == 0) return CMPC_OK;
+  if (B > pl->p.max_batch) return fail(CMPC_E_RANGE, w + ": B exceeds plan max_batch");
+  if (!in.Ad || !in.Bd || !in.gd || !in.x0 || !in.xref || !in.contact || !out.w || !out.status ||
+      !out.iters)
+    return fail(CMPC_E_INVALID, w + ": null array argument");
+  out.stats = pl->d_stats;
+  return solve_impl(pl, B, in, out, stream);
+}
+
 int cmpc_solve(cmpc_plan* pl, int64_t B, const float* Ad, const float* Bd, const float* gd,
                const float* x0, const float* xref, const uint8_t* contact, float* w_out,
                int32_t* status, int32_t* iters, void* stream) {
-  if (!pl) return fail(CMPC_E_INVALID, "cmpc_solve: null plan");
-  if (B < 0) return fail(CMPC_E_INVALID, "cmpc_solve: negative batch");
-  if (B == 0) return CMPC_OK;
-  if (B > pl->p.max_batch) return fail(CMPC_E_RANGE, "cmpc_solve: B exceeds plan max_batch");
-  if (!Ad || !Bd || !gd || !x0 || !xref || !contact || !w_out || !status || !iters)
-    return fail(CMPC_E_INVALID, "cmpc_solve: null array argument");
-  return solve_impl(pl, B, cmpc::Inputs{Ad, Bd, gd, x0, xref, contact, nullptr, nullptr, nullptr},
-                    cmpc::Outputs{w_out, status, iters, nullptr, nullptr, pl->d_stats}, stream);
+  return solve_checked(pl, B,
+                       cmpc::Inputs{Ad, Bd, gd, x0, xref, contact, nullptr, nullptr, nullptr, nullptr, nullptr},
+                       cmpc::Outputs{w_out, status, iters, nullptr, nullptr, nullptr}, stream, "cmpc_solve");
 }
 
 int cmpc_solve_warm(cmpc_plan* pl, int64_t B, const float* Ad, const float* Bd,
                     const float* gd, const float* x0, const float* xref,
                     const uint8_t* contact, const float* w_init, const float* y_init,
                     float* w_out, float* y_out, int32_t* status, int32_t* iters, void* stream) {
-  if (!pl) return fail(CMPC_E_INVALID, "cmpc_solve_warm: null plan");
-  if (B < 0) return fail(CMPC_E_INVALID, "cmpc_solve_warm: negative batch");
-  if (B == 0) return CMPC_OK;
-  if (B > pl->p.max_batch) return fail(CMPC_E_RANGE, "cmpc_solve_warm: B exceeds plan max_batch");
-  if (!Ad || !Bd || !gd || !x0 || !xref || !contact || !w_out || !status || !iters)
-    return fail(CMPC_E_INVALID, "cmpc_solve_warm: null array argument");
-  return solve_impl(pl, B, cmpc::Inputs{Ad, Bd, gd, x0, xref, contact, w_init, y_init, nullptr},
-                    cmpc::Outputs{w_out, status, iters, y_out, nullptr, pl->d_stats}, stream);
+  return solve_checked(pl, B,
+                       cmpc::Inputs{Ad, Bd, gd, x0, xref, contact, w_init, y_init, nullptr, nullptr, nullptr},
+                       cmpc::Outputs{w_out, status, iters, y_out, nullptr, nullptr}, stream,
+                       "cmpc_solve_warm");
 }
 
 int cmpc_solve_ref(cmpc_plan* pl, int64_t B, const float* Ad, const float* Bd, const float* gd,
                    const float* x0, const float* xref, const uint8_t* contact,
                    const float* w_init, const float* lam_init, float* w_out, float* lam_out,
                    int32_t* status, int32_t* iters, void* stream) {
-  if (!pl) return fail(CMPC_E_INVALID, "cmpc_solve_ref: null plan");
-  if (B < 0) return fail(CMPC_E_INVALID, "cmpc_solve_ref: negative batch");
-  if (B == 0) return CMPC_OK;
-  if (B > pl->p.max_batch) return fail(CMPC_E_RANGE, "cmpc_solve_ref: B exceeds plan max_batch");
-  if (!Ad || !Bd || !gd || !x0 || !xref || !contact || !w_out || !status || !iters)
-    return fail(CMPC_E_INVALID, "cmpc_solve_ref: null array argument");
-  return solve_impl(pl, B, cmpc::Inputs{Ad, Bd, gd, x0, xref, contact, w_init, nullptr, lam_init},
-                    cmpc::Outputs{w_out, status, iters, nullptr, lam_out, pl->d_stats}, stream);
+  return solve_checked(pl, B,
+                       cmpc::Inputs{Ad, Bd, gd, x0, xref, contact, w_init, nullptr, lam_init, nullptr, nullptr},
+                       cmpc::Outputs{w_out, status, iters, nullptr, lam_out, nullptr}, stream,
+                       "cmpc_solve_ref");
+}
+
+int cmpc_solve_io_run(cmpc_plan* pl, int64_t B, const cmpc_solve_io* io, void* stream) {
+  // (the struct is checked before the plan is touched)
+  if (!io) return fail(CMPC_E_INVALID, "cmpc_solve_io_run: null io");
+  // fields past the caller's size are NULL (the struct grows at its end)
+  cmpc_solve_io a;
+  memset(&a, 0, sizeof(a));
+  if (io->size < offsetof(cmpc_solve_io, Ad))
+    return fail(CMPC_E_INVALID, "cmpc_solve_io_run: io->size is not a cmpc_solve_io size");
+  memcpy(&a, io, std::min((size_t)io->size, sizeof(a)));
+  if ((a.y_init || a.y_out) && (a.lam_init || a.lam_out))
+    return fail(CMPC_E_INVALID, "cmpc_solve_io_run: y_init / y_out (this solver's dual) and "
+                                "lam_init / lam_out (the reference's multipliers) are exclusive");
+  return solve_checked(pl, B,
+                       cmpc::Inputs{a.Ad, a.Bd, a.gd, a.x0, a.xref, a.contact, a.w_init, a.y_init,
+                                    a.lam_init, a.mu, a.fz_min},
+                       cmpc::Outputs{a.w_out, a.status, a.iters, a.y_out, a.lam_out, nullptr}, stream,
+                       "cmpc_solve_io_run");
 }
 
 // group k's persistent kernel with g waves whose park slabs start at wave w0 of the group's

@@ -59,6 +59,24 @@ __device__ __forceinline__ float uniformf(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
 }
 
+// One instance's friction coefficient and stance fz floor (Inputs::mu / fz_min, or the plan's
+// constants).  The instance index is wave-uniform, so both are read through uniformf and live in
+// scalar registers for the whole solve: no per-lane state (the solve kernels sit at the register
+// ceiling).
+struct Terrain {
+  float mu, fz_min;
+};
+__device__ __forceinline__ Terrain instance_terrain(const KParams& P, const Inputs& in, int64_t b) {
+  Terrain T{P.mu, P.fz_min};
+  if (in.mu) T.mu = uniformf(in.mu[b]);
+  if (in.fz_min) T.fz_min = uniformf(in.fz_min[b]);
+  return T;
+}
+// (cmpc_plan_create's test of the plan's constants; false also for NaN)
+__device__ __forceinline__ bool terrain_valid(const Terrain& T) {
+  return T.mu > 0.f && isfinite(T.mu) && isfinite(T.fz_min);
+}
+
 // v[l] and v[l ^ 32] (resp. v[l ^ 16]) without address registers (gfx950 permlane swaps):
 // after the swap the two results hold the lane's own value and its partner's in some order
 __device__ __forceinline__ void pair32(float v, float& a, float& b) {
@@ -1501,12 +1519,12 @@ __device__ __forceinline__ void build_admm_basis(Smem<NC>& s, const KParams& P,
 // written, since s.dl shares the G slab).  Returns nr; the param indices of each triple are
 // left packed in s.fpk for the KKT check.
 template <int NC>
-__device__ __forceinline__ int polish_setup(Smem<NC>& s, const KParams& P,
+__device__ __forceinline__ int polish_setup(Smem<NC>& s, const KParams& P, const Terrain& T,
                                             const float* __restrict__ Bg, int ntri,
                                             const float* vsrc) {
   const int lane = opaque_lane();
   const int N = P.N;
-  const float mu = P.mu, fzmin = P.fz_min;
+  const float mu = T.mu, fzmin = T.fz_min;
   WSYNC();
   const bool owns = lane < ntri;
   float vs[3] = {0.f, 0.f, 0.f};
@@ -1604,13 +1622,13 @@ __device__ __forceinline__ int polish_setup(Smem<NC>& s, const KParams& P,
 // top > 0: the repair changes only the `top` triples with the largest relative violation (the
 // others keep their faces).
 template <int NC>
-__device__ __forceinline__ bool polish_check(Smem<NC>& s, const KParams& P,
+__device__ __forceinline__ bool polish_check(Smem<NC>& s, const KParams& P, const Terrain& T,
                                              const float* __restrict__ Bg, int ntri, float step,
                                              bool& changed, bool& loose, bool& converged,
                                              bool& amb, bool& decisive, float& vworst,
                                              int top = 0, int tr = -1) {
   const int lane = opaque_lane();
-  const float mu = P.mu, fzmin = P.fz_min;
+  const float mu = T.mu, fzmin = T.fz_min;
   float fx = 0.f, fy = 0.f, fz = 0.f;
   float gx = 0.f, gy = 0.f, gz = 0.f;
   bool lok = true;
@@ -1823,8 +1841,8 @@ __device__ __forceinline__ float* dd_meta(Smem<NC>& s) { return s.H + kMaxP - 32
 // the faces held so far.  False if they do not fit or a d_j is not positive (rounding after
 // many downdates): the caller refactors.
 template <int NC, class MT>
-__device__ __forceinline__ bool face_downdate(Smem<NC>& s, const KParams& P, const MT& M, int n,
-                                              int ntri, int& nadd) {
+__device__ __forceinline__ bool face_downdate(Smem<NC>& s, const KParams& P, const Terrain& T,
+                                              const MT& M, int n, int ntri, int& nadd) {
   static_assert(dd_max(NC) >= 1 && dd_max(NC) <= 8, "the meta block holds 8 faces");
   static_assert(offsetof(Smem<NC>, H) == offsetof(Smem<NC>, ds) + 5 * NC * sizeof(float),
                 "ds, pan and H are one slab");
@@ -1843,7 +1861,7 @@ __device__ __forceinline__ bool face_downdate(Smem<NC>& s, const KParams& P, con
     if (nadd + F > dd_max(NC)) return false;  // (uniform)
     if (owns && add) {
       // a face with no second param has p2 = p1 and coefficient 0
-      const float mu = P.mu, fzmin = P.fz_min;
+      const float mu = T.mu, fzmin = T.fz_min;
       const int pk = s.fpk[lane];
       const int px = pk & 255, py = (pk >> 8) & 255, pz = (pk >> 16) & 255;
       if (add & 1) {  // (first: a friction face added with it then reads fz = fz_min)
@@ -1996,6 +2014,7 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
   const int lane = opaque_lane();
   const int N = P.N;
   const int NP = 12 * N;
+  const Terrain T = instance_terrain(P, in, b);
 #if defined(CMPC_POISON_LDS)  // diagnostic: NaN into the float scratch before every instance
   if constexpr (W == 1) {
     const float qn = __int_as_float(0x7fc00000);
@@ -2042,8 +2061,10 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
     for (int i = 0; i < 4; ++i) s.G[lane + 64 * i] = rv[i];
     if (lane < 12) s.G[256 + lane] = gv;
   }
-  // stance triples in (k, leg) order; lane = 4k + leg
-  const bool stc = (lane < 4 * N) ? (ctb[(lane & 3) * N + (lane >> 2)] != 0) : false;
+  // stance triples in (k, leg) order; lane = 4k + leg.  An instance whose mu / fz_min entry is
+  // invalid has no feasible set to solve on: it takes the all-swing path (zero forces, X = the
+  // rollout) and returns status -10
+  const bool stc = (lane < 4 * N && terrain_valid(T)) ? (ctb[(lane & 3) * N + (lane >> 2)] != 0) : false;
   const int pos = wave_excl_scan4(stc ? 1 : 0);
   const int ntri = wave_total4(stc ? 1 : 0);
   if (stc) s.tri[pos] = lane;
@@ -2108,7 +2129,7 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
       const float f0 = lf[0], f1 = lf[1], f2 = lf[2], f3 = lf[3];
       yv[0] = f0 - f1 + lx[0];
       yv[1] = f2 - f3 + lx[1];
-      yv[2] = -P.mu * (f0 + f1 + f2 + f3) + lx[2];
+      yv[2] = -T.mu * (f0 + f1 + f2 + f3) + lx[2];
     }
 #pragma unroll
     for (int a = 0; a < 3; ++a) {  // non-finite warm data falls back to a cold start
@@ -2116,15 +2137,15 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
       if (!isfinite(yv[a])) yv[a] = 0.f;
     }
     float pv[3], qv[3];
-    project(u[0], u[1], u[2], P.mu, P.fz_min, pv[0], pv[1], pv[2]);
+    project(u[0], u[1], u[2], T.mu, T.fz_min, pv[0], pv[1], pv[2]);
     int code;
     if (in.y_init || in.lam_init) {  // the dual pushes the faces it holds outward (at the bin's initial rho)
       const float ir = 1.f / rho;
-      code = project(pv[0] + yv[0] * ir, pv[1] + yv[1] * ir, pv[2] + yv[2] * ir, P.mu, P.fz_min,
+      code = project(pv[0] + yv[0] * ir, pv[1] + yv[1] * ir, pv[2] + yv[2] * ir, T.mu, T.fz_min,
                      qv[0], qv[1], qv[2]);
     } else {          // primal only: the faces the warm point lies on, to fp32 rounding
-      const float tz = 1e-5f * fmaxf(pv[2], 1.f), lim = P.mu * pv[2] - 1e-5f * pv[2];
-      code = (pv[2] <= P.fz_min + tz) ? 1 : 0;
+      const float tz = 1e-5f * fmaxf(pv[2], 1.f), lim = T.mu * pv[2] - 1e-5f * pv[2];
+      code = (pv[2] <= T.fz_min + tz) ? 1 : 0;
       code |= (pv[0] >= lim) ? 2 : (pv[0] <= -lim) ? 4 : 0;
       code |= (pv[1] >= lim) ? 8 : (pv[1] <= -lim) ? 16 : 0;
     }
@@ -2182,7 +2203,7 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
     WSYNC();
     if (lane < ntri) s.code[lane] = s.pcode[lane];
     repairs_left = session_start<NC>(s, P, ntri, nfail, ntried, seen_start);
-    nact = polish_setup<NC>(s, P, Bg, ntri, s.z);
+    nact = polish_setup<NC>(s, P, T, Bg, ntri, s.z);
     shift = P.sigma;
     in_polish = true;
   }
@@ -2257,10 +2278,10 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
         const int top = (kRepairTop > 0 && (nfail > 0 || ntried >= 3)) ? kRepairTop : 0;
         bool amb = false;
   #ifdef CMPC_TRACE
-        ok = polish_check<NC>(s, P, Bg, ntri, step, changed, loose, converged, amb, decisive,
+        ok = polish_check<NC>(s, P, T, Bg, ntri, step, changed, loose, converged, amb, decisive,
                               vworst, top, trace_on(b) ? (int)b : -1);
   #else
-        ok = polish_check<NC>(s, P, Bg, ntri, step, changed, loose, converged, amb, decisive,
+        ok = polish_check<NC>(s, P, T, Bg, ntri, step, changed, loose, converged, amb, decisive,
                               vworst, top);
   #endif
         amb_last = amb;
@@ -2329,7 +2350,7 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
 #ifdef CMPC_TRACE
         if (trace_on(b) && lane == 0) printf("[%d] it %d STALL-REFACTOR dd_stall %d\n", (int)b, it, (int)dd_stall);
 #endif
-        nact = polish_setup<NC>(s, P, Bg, ntri, s.dl);
+        nact = polish_setup<NC>(s, P, T, Bg, ntri, s.dl);
         nadd = 0;
         shift = P.sigma;
         refactor = true;
@@ -2357,7 +2378,7 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
 #endif
           if (__any((nc & oc) != oc) == 0 && nadd + nf <= dd_max(NC)) {  // (uniform)
             CMPC_T0(t_dd);
-            dd = face_downdate<NC>(s, P, M, nact, ntri, nadd);
+            dd = face_downdate<NC>(s, P, T, M, nact, ntri, nadd);
 #ifdef CMPC_TRACE
             if (trace_on(b) && lane == 0)
               printf("[%d] it %d downdate nf %d -> %d nadd %d\n", (int)b, it, nf, (int)dd, nadd);
@@ -2373,7 +2394,7 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
         }
         if (ntried < kTryMem) ++ntried;
         if (dd) continue;  // refine on the downdated inverse
-        nact = polish_setup<NC>(s, P, Bg, ntri, s.z);
+        nact = polish_setup<NC>(s, P, T, Bg, ntri, s.z);
         nadd = 0;
         shift = P.sigma;
         refactor = true;
@@ -2388,7 +2409,7 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
         WSYNC();
         if (l < ntri) {  // (projected onto the pyramid: the loose check admits 5x polish_tol)
           float px, py, pz;
-          project(s.dl[3 * l], s.dl[3 * l + 1], s.dl[3 * l + 2], P.mu, P.fz_min, px, py, pz);
+          project(s.dl[3 * l], s.dl[3 * l + 1], s.dl[3 * l + 2], T.mu, T.fz_min, px, py, pz);
           s.x[3 * l] = px;
           s.x[3 * l + 1] = py;
           s.x[3 * l + 2] = pz;
@@ -2528,7 +2549,7 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
           w[a] = xr[a] + s.y[p] * inv_rho;
         }
         float pv[3];
-        const int code = project(w[0], w[1], w[2], P.mu, P.fz_min, pv[0], pv[1], pv[2]);
+        const int code = project(w[0], w[1], w[2], T.mu, T.fz_min, pv[0], pv[1], pv[2]);
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
           const int p = 3 * l + a;
@@ -2604,7 +2625,7 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
         }
       }
       repairs_left = session_start<NC>(s, P, ntri, nfail, ntried, seen_start);
-      nact = polish_setup<NC>(s, P, Bg, ntri, s.z);
+      nact = polish_setup<NC>(s, P, T, Bg, ntri, s.z);
       nadd = 0;
 #ifdef CMPC_TRACE
       if (trace_on(b) && lane == 0)
@@ -2642,7 +2663,7 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
     wb[o] = xv;
     wb[NP + o] = uv;
   }
-  if (__any(bad)) status = -10;
+  if (__any(bad) || !terrain_valid(T)) status = -10;
 #ifdef CMPC_DIAG_COUNTS  // diagnostic build: w[0..7] = cycles and factorizations at failed sessions 1..4
   if (lane < 4) wb[lane] = dg_fail_t[lane];
   else if (lane < 8) wb[lane] = (float)dg_fail_f[lane - 4];
@@ -2696,8 +2717,8 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
         if (polished) {
           code = s.code[t];
         } else {  // faces the forces lie on, to fp32 rounding
-          const float tz = 1e-5f * fmaxf(u[2], 1.f), lim = P.mu * u[2] - 1e-5f * fmaxf(u[2], 1.f);
-          code = (u[2] <= P.fz_min + tz) ? 1 : 0;
+          const float tz = 1e-5f * fmaxf(u[2], 1.f), lim = T.mu * u[2] - 1e-5f * fmaxf(u[2], 1.f);
+          code = (u[2] <= T.fz_min + tz) ? 1 : 0;
           code |= (u[0] >= lim) ? 2 : (u[0] <= -lim) ? 4 : 0;
           code |= (u[1] >= lim) ? 8 : (u[1] <= -lim) ? 16 : 0;
         }
@@ -2706,7 +2727,7 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
         if (code & 4) lf[1] = fmaxf(sv[0], 0.f);
         if (code & 8) lf[2] = fmaxf(-sv[1], 0.f);
         if (code & 16) lf[3] = fmaxf(sv[1], 0.f);
-        if (code & 1) lxv[2] = fminf(-(sv[2] - P.mu * (lf[0] + lf[1] + lf[2] + lf[3])), 0.f);
+        if (code & 1) lxv[2] = fminf(-(sv[2] - T.mu * (lf[0] + lf[1] + lf[2] + lf[3])), 0.f);
       }
       float* lxo = lb + NP + 12 * k + 3 * leg;
 #pragma unroll

@@ -47,7 +47,8 @@
  *                                     2 solved inaccurate: ADMM residuals within eps, or a polished
  *                                       point that misses the certified bound (returned, but not
  *                                       verified to 1e-4),
- *                                     -2 max iterations, -10 numerical failure
+ *                                     -2 max iterations, -10 numerical failure or an invalid
+ *                                       per-instance mu / fz_min entry (cmpc_solve_io)
  *   iters   [B]                int32  ADMM iterations taken
  *
  * Threading: one plan per host thread / stream.  cmpc_solve is asynchronous on `stream`
@@ -170,6 +171,41 @@ int cmpc_solve_ref(cmpc_plan* plan, int64_t B, const float* Ad, const float* Bd,
                    const float* x0, const float* xref, const uint8_t* contact,
                    const float* w_init, const float* lam_init, float* w_out, float* lam_out,
                    int32_t* status, int32_t* iters, void* stream);
+
+/* Every argument of a solve in one struct; the entry that takes per-instance terrain.  It covers
+ * cmpc_solve, cmpc_solve_warm and cmpc_solve_ref (which are wrappers over the same launch) and
+ * adds:
+ *   mu      [B]  fp32  nullable; the friction coefficient of instance b (NULL: params.mu)
+ *   fz_min  [B]  fp32  nullable; its stance normal-force lower bound (NULL: params.fz_min)
+ * The kernels read both arrays when they run, one wave-uniform value per instance: a captured
+ * graph sees values the caller has since written in place, and a terrain estimator can change a
+ * robot's mu from one tick to the next without a new plan.  NULL, or an array filled with the
+ * plan's constant, computes bit for bit what the plan's constant computes.
+ * An entry is invalid when mu is not finite, mu <= 0 or fz_min is not finite.  An invalid entry
+ * never fails the call: that instance returns status -10 with zero forces and X = the rollout
+ * of zero forces (the path an instance with no stance leg takes), its y_out row is zero, and
+ * every other instance of the batch is solved as if the entry were valid.
+ * `size` is the caller's sizeof of the struct: fields past it are read as NULL, so the struct
+ * can grow at its end without an ABI bump.  The inputs Ad..contact and the outputs w_out,
+ * status, iters are required; w_init, y_init / y_out and lam_init / lam_out are as for
+ * cmpc_solve_warm / cmpc_solve_ref.  The y pair (this solver's dual) and the lam pair (the
+ * reference's multipliers) are exclusive: one of each together is CMPC_E_INVALID.
+ * Same guarantees as cmpc_solve: asynchronous on `stream`, no allocation, no host
+ * synchronisation, graph-capturable. */
+typedef struct cmpc_solve_io {
+  uint32_t size;            /* sizeof of this struct in the caller's header */
+  /* inputs, layouts as cmpc_solve */
+  const float *Ad, *Bd, *gd, *x0, *xref;
+  const uint8_t* contact;
+  const float* mu;          /* [B] nullable */
+  const float* fz_min;      /* [B] nullable */
+  const float *w_init, *y_init, *lam_init; /* nullable */
+  /* outputs */
+  float *w_out, *y_out, *lam_out;          /* y_out, lam_out nullable */
+  int32_t *status, *iters;
+} cmpc_solve_io;
+
+int cmpc_solve_io_run(cmpc_plan* plan, int64_t B, const cmpc_solve_io* io, void* stream);
 
 void cmpc_plan_destroy(cmpc_plan* plan);
 
