@@ -119,10 +119,12 @@ class CentroidalMPC:
         print(f"  vars: {self.nvars:d} | constr: {nA_rows:d} | horizon N = {N}")
         print("[QP Init] ✓ Initialization complete.\n")
 
-    def solve_QP(self, go2, traj, verbose: bool = False, *, mu=None, fz_min=None):
+    def solve_QP(self, go2, traj, verbose: bool = False, *, mu=None, fz_min=None, Q=None,
+                 R=None):
         """The reference's solve_QP.  ``mu`` / ``fz_min`` (keyword only, beyond the reference):
         this tick's friction coefficient and stance normal-force floor for the robot; None
-        keeps the module constants MU / FZ_MIN."""
+        keeps the module constants MU / FZ_MIN.  ``Q`` / ``R`` (keyword only): this tick's 12
+        state weights and 12 input weights (the diagonals); None keeps the plan's."""
         torch = self._torch
         t0 = time.perf_counter()
         N = self.N
@@ -149,6 +151,10 @@ class CentroidalMPC:
         for name, v in (("mu", mu), ("fz_min", fz_min)):
             if v is not None:
                 kw[name] = torch.full((1,), float(v), dtype=torch.float32, device=self.plan.device)
+        for name, v in (("Q", Q), ("R", R)):
+            if v is not None:
+                kw[name] = torch.as_tensor(np.asarray(v, np.float32).reshape(1, 12),
+                                           device=self.plan.device)
         w, st, it = self.plan.solve(b["Ad"], b["Bd"], b["gd"], b["x0"], b["xref"], b["contact"],
                                     out=self._out, lam_out=self._lam, **kw)
         self._warm = True

@@ -47,12 +47,12 @@ class CParams(ctypes.Structure):
 
 
 class CSolveIO(ctypes.Structure):
-    """cmpc_solve_io (include/cmpc.h): every argument of a solve, per-instance mu / fz_min
-    included.  ``size`` is this mirror's sizeof."""
+    """cmpc_solve_io (include/cmpc.h): every argument of a solve, per-instance mu / fz_min and
+    cost weights Q / R included.  ``size`` is this mirror's sizeof."""
     _fields_ = ([("size", ctypes.c_uint32)] +
                 [(n, ctypes.c_void_p) for n in
                  ("Ad", "Bd", "gd", "x0", "xref", "contact", "mu", "fz_min", "w_init", "y_init",
-                  "lam_init", "w_out", "y_out", "lam_out", "status", "iters")])
+                  "lam_init", "w_out", "y_out", "lam_out", "status", "iters", "Q", "R")])
 
 
 EXPORTS = ("cmpc_params_default", "cmpc_plan_create", "cmpc_solve", "cmpc_plan_destroy",

@@ -6,7 +6,7 @@ until the next MPC tick; MuJoCo integrates the robot.  Here one call of :meth:`C
 does that for B robots with no host round trip:
 
   cmpc_generate_traj -> cmpc_build_dynamics -> cmpc_solve_warm (cmpc_solve_io_run with
-  per-robot terrain) -> cmpc_srb_step (nsub substeps)
+  per-robot terrain or weights) -> cmpc_srb_step (nsub substeps)
 
 MuJoCo and the Go2 model are absent from this image, so the plant is ``cmpc_srb_step``'s
 single-rigid-body stand-in (include/cmpc.h) and the robot quantities Pinocchio would supply are
@@ -43,11 +43,16 @@ class ClosedLoop:
     / ``self.fz_min`` and passes them to every solve by pointer: writing new values into them in
     place (``loop.mu.copy_(...)``, a terrain estimator's output) takes effect at the next tick,
     a replay of the captured graph included.  They bound the forces the MPC plans; the
-    single-rigid-body plant has no friction model and applies the planned forces as they are."""
+    single-rigid-body plant has no friction model and applies the planned forces as they are.
+
+    ``Q`` / ``R``: per-robot cost weights, (B, 12) or (12,) values (None: the plan's constants),
+    kept the same way as the device tensors ``self.Q`` / ``self.R``: a supervisor that writes a
+    robot's row in place re-weights that robot from the next tick on."""
 
     def __init__(self, B: int, plan: Optional[Plan] = None, gait_hz: float = synth.GAIT_HZ,
                  duty: float = synth.GAIT_DUTY, offsets=synth.TROT_OFFSETS, nsub: int = 20,
-                 seed: int = 0, device="cuda", shift_warm: bool = True, mu=None, fz_min=None):
+                 seed: int = 0, device="cuda", shift_warm: bool = True, mu=None, fz_min=None,
+                 Q=None, R=None):
         self.plan = plan or Plan(SolverParams(max_batch=B))
         self.B, self.N = B, self.plan.params.N
         dev = torch.device(device)
@@ -96,6 +101,10 @@ class ClosedLoop:
             None if v is None else
             torch.as_tensor(v, dtype=f32).expand(B).contiguous().to(dev, copy=True)
             for v in (mu, fz_min))
+        self.Q, self.R = (
+            None if v is None else
+            torch.as_tensor(v, dtype=f32).expand(B, 12).contiguous().to(dev, copy=True)
+            for v in (Q, R))
         self.shift_warm = shift_warm
         self.warm = False
         self.graph = None
@@ -130,7 +139,7 @@ class ClosedLoop:
             kw = dict(w_init=self.w, y_init=self.y) if warm else {}
         p.solve(self.Ad, self.Bd, self.gd, self.x, self.xref, self.ct,
                 out=(self.w, self.status, self.iters), stream=stream, y_out=self.y,
-                mu=self.mu, fz_min=self.fz_min, **kw)
+                mu=self.mu, fz_min=self.fz_min, Q=self.Q, R=self.R, **kw)
         sp = ctypes.c_void_p(stream.cuda_stream)
         P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
         force = self.w[:, 12 * N:]                        # U[:, 0] rows (test_MPC.py:196)

@@ -13,6 +13,7 @@ import torch.distributed as dist
 
 FIELDS = ("Ad", "Bd", "gd", "x0", "xref", "contact")
 TERRAIN = ("mu", "fz_min")    # optional (B,) stacks: per-instance terrain (Plan.solve)
+WEIGHTS = ("Q", "R")          # optional (B, 12) stacks: per-instance cost weights (Plan.solve)
 
 
 def shard_bounds(B: int, rank: int, world: int):
@@ -25,7 +26,7 @@ def shard_bounds(B: int, rank: int, world: int):
 def shard_batch(batch: dict, rank: int, world: int) -> dict:
     B = batch["Ad"].shape[0]
     lo, hi = shard_bounds(B, rank, world)
-    return {k: batch[k][lo:hi] for k in FIELDS + tuple(t for t in TERRAIN if t in batch)}
+    return {k: batch[k][lo:hi] for k in FIELDS + tuple(t for t in TERRAIN + WEIGHTS if t in batch)}
 
 
 def _pad_chunks(t: torch.Tensor, world: int):
@@ -42,17 +43,18 @@ def _pad_chunks(t: torch.Tensor, world: int):
 
 
 def scatter_batch(batch: dict | None, B: int, N: int, device, group=None,
-                  terrain: bool = False) -> dict:
+                  terrain: bool = False, weights: bool = False) -> dict:
     """Rank 0 holds `batch` (tensors on `device`); every rank receives its shard.  All ranks
     pass the global B and horizon N.  terrain=True (on every rank: each stack is one
-    collective) also scatters the (B,) fp32 stacks `mu` and `fz_min` of rank 0's batch."""
+    collective) also scatters the (B,) fp32 stacks `mu` and `fz_min` of rank 0's batch,
+    weights=True the (B, 12) fp32 stacks `Q` and `R`."""
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     lo, hi = shard_bounds(B, rank, world)
     per = (B + world - 1) // world
     shapes = {"Ad": (12, 12), "Bd": (N, 12, 12), "gd": (12,), "x0": (12,), "xref": (N, 12),
-              "contact": (4, N), "mu": (), "fz_min": ()}
+              "contact": (4, N), "mu": (), "fz_min": (), "Q": (12,), "R": (12,)}
     out = {}
-    for k in FIELDS + (TERRAIN if terrain else ()):
+    for k in FIELDS + (TERRAIN if terrain else ()) + (WEIGHTS if weights else ()):
         dt = torch.uint8 if k == "contact" else torch.float32
         recv = torch.empty((per,) + shapes[k], dtype=dt, device=device)
         if rank == 0:

@@ -188,7 +188,8 @@ class Plan:
         return list(ms)[:k], list(calls)[:k]
 
     def solve(self, Ad, Bd, gd, x0, xref, contact, out=None, stream=None, w_init=None,
-              y_init=None, y_out=None, lam_init=None, lam_out=None, mu=None, fz_min=None):
+              y_init=None, y_out=None, lam_init=None, lam_out=None, mu=None, fz_min=None,
+              Q=None, R=None):
         """Solve B instances; all inputs are device tensors (layouts: include/cmpc.h).
 
         Returns (w (B, 24N) fp32, status (B,) int32, iters (B,) int32).  Asynchronous on
@@ -210,7 +211,13 @@ class Plan:
         None takes the plan's constant.  They combine with every option above.  The kernels
         read them when they run, so a captured graph sees values written in place since.  An
         instance whose entry is invalid (mu not finite or <= 0, fz_min not finite) returns
-        status -10 with zero forces; the others are unaffected."""
+        status -10 with zero forces; the others are unaffected.
+
+        Per-instance cost weights (the same entry): ``Q`` (B, 12) the state-weight diagonal and
+        ``R`` (B, 12) the input-weight diagonal of each instance, fp32 device tensors in the
+        order of ``SolverParams.Q`` / ``R``; None takes the plan's constants.  Same rules: read
+        when the kernels run, combinable with every option, and a row with a Q entry negative
+        or not finite or an R entry <= 0 or not finite returns status -10 with zero forces."""
         N = self.params.N
         B = Ad.shape[0]
         f32 = torch.float32
@@ -236,9 +243,9 @@ class Plan:
         if stream is None:
             stream = torch.cuda.current_stream(Ad.device)
         sp = ctypes.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else stream)
-        if mu is not None or fz_min is not None:
+        if mu is not None or fz_min is not None or Q is not None or R is not None:
             return self._solve_io(B, (Ad, Bd, gd, x0, xref, contact), (w, status, iters), sp,
-                                  w_init, y_init, y_out, lam_init, lam_out, mu, fz_min)
+                                  w_init, y_init, y_out, lam_init, lam_out, mu, fz_min, Q, R)
         if lam_init is not None or lam_out is not None:
             if y_init is not None or y_out is not None:
                 raise ValueError("lam_init/lam_out (reference layout) and y_init/y_out "
@@ -288,11 +295,12 @@ class Plan:
             return w, status, iters, y_out
         return w, status, iters
 
-    def _solve_io(self, B, inputs, outs, sp, w_init, y_init, y_out, lam_init, lam_out, mu, fz_min):
-        """solve() with per-instance mu / fz_min: the struct entry cmpc_solve_io_run."""
+    def _solve_io(self, B, inputs, outs, sp, w_init, y_init, y_out, lam_init, lam_out, mu, fz_min,
+                  Q=None, R=None):
+        """solve() with per-instance mu / fz_min / Q / R: the struct entry cmpc_solve_io_run."""
         if not hasattr(self.lib, "cmpc_solve_io_run"):
             raise CmpcError("cmpc: this libcmpc.so has no cmpc_solve_io_run: per-instance mu / "
-                            "fz_min need a library built from sources that declare it")
+                            "fz_min / Q / R need a library built from sources that declare it")
         if (lam_init is not None or lam_out is not None) and (y_init is not None or y_out is not None):
             raise ValueError("lam_init/lam_out (reference layout) and y_init/y_out "
                              "(cmpc layout) are exclusive")
@@ -304,7 +312,8 @@ class Plan:
             y_out = torch.empty((B, 12 * N), dtype=f32, device=dev)
         if ret_l:
             lam_out = torch.empty((B, 52 * N), dtype=f32, device=dev)
-        opt = dict(mu=(mu, (B,)), fz_min=(fz_min, (B,)), w_init=(w_init, (B, 24 * N)),
+        opt = dict(mu=(mu, (B,)), fz_min=(fz_min, (B,)), Q=(Q, (B, 12)), R=(R, (B, 12)),
+                   w_init=(w_init, (B, 24 * N)),
                    y_init=(y_init, (B, 12 * N)), lam_init=(lam_init, (B, 52 * N)),
                    y_out=(y_out, (B, 12 * N)), lam_out=(lam_out, (B, 52 * N)))
         io = _lib.CSolveIO()
@@ -461,7 +470,8 @@ def to_device_batch(batch: dict, device="cuda") -> dict:
     for k in ("Ad", "Bd", "gd", "x0", "xref"):
         out[k] = torch.as_tensor(batch[k], dtype=torch.float32).contiguous().to(device)
     out["contact"] = torch.as_tensor(batch["contact"], dtype=torch.uint8).contiguous().to(device)
-    for k in ("mu", "fz_min"):      # per-instance terrain (synth.make_terrain), when present
+    # per-instance terrain (synth.make_terrain) and weights (synth.make_weights), when present
+    for k in ("mu", "fz_min", "Q", "R"):
         if batch.get(k) is not None:
             out[k] = torch.as_tensor(batch[k], dtype=torch.float32).contiguous().to(device)
     return out
@@ -472,6 +482,6 @@ def solve_batch(batch: dict, params: Optional[SolverParams] = None, plan: Option
     plan = plan or Plan(params)
     d = to_device_batch(batch, plan.device)
     w, st, it = plan.solve(d["Ad"], d["Bd"], d["gd"], d["x0"], d["xref"], d["contact"],
-                           mu=d.get("mu"), fz_min=d.get("fz_min"))
+                           mu=d.get("mu"), fz_min=d.get("fz_min"), Q=d.get("Q"), R=d.get("R"))
     torch.cuda.synchronize(plan.device)
     return w.cpu().numpy(), st.cpu().numpy(), it.cpu().numpy()

@@ -208,6 +208,30 @@ def make_terrain(B: int, seed: int, mu=(0.2, 1.0), fz_min=(0.0, 20.0)) -> dict:
     return dict(mu=draw(*mu), fz_min=draw(*fz_min))
 
 
+Q_DEFAULT = (1, 1, 50, 10, 20, 1, 2, 2, 1, 1, 1, 1)   # SolverParams.Q (centroidal_mpc.py:12)
+
+
+def make_weights(B: int, seed: int, q_span: float = 4.0, r=(2.5e-6, 1e-4)) -> dict:
+    """Per-instance cost weights for a batch of ``B``, the ``Q`` / ``R`` arrays of
+    ``cmpc_solve_io`` (include/cmpc.h): ``Q`` (B, 12) = the default state weights x
+    exp(U(-ln q_span, ln q_span)) per entry, drawn first, then ``R`` (B, 12) log-uniform in ``r``
+    per entry.  float64 arrays of fp32-representable values inside the closed ranges.  Its
+    generator is its own: the draws of :func:`make_batch` do not depend on it."""
+    rng = np.random.default_rng(seed)
+    q0 = np.asarray(Q_DEFAULT, np.float64)
+
+    def clip32(v, lo, hi):
+        lo32, hi32 = lo.astype(np.float32), hi.astype(np.float32)
+        lo32 = np.where(lo32 < lo, np.nextafter(lo32, np.float32(np.inf)), lo32)
+        hi32 = np.where(hi32 > hi, np.nextafter(hi32, np.float32(-np.inf)), hi32)
+        return np.clip(v.astype(np.float32), lo32, hi32).astype(np.float64)
+    ls = np.log(q_span)
+    Q = clip32(q0 * np.exp(rng.uniform(-ls, ls, (B, 12))), q0 / q_span + 0 * q0, q0 * q_span)
+    lo, hi = np.float64(r[0]), np.float64(r[1])
+    R = clip32(np.exp(rng.uniform(np.log(lo), np.log(hi), (B, 12))), lo + 0 * q0, hi + 0 * q0)
+    return dict(Q=Q, R=R)
+
+
 CONFIGS = {
     0: dict(B=1, seed=0, mixed=False),
     1: dict(B=256, seed=1, mixed=False),

@@ -37,6 +37,8 @@ struct Inputs {
   const float* lam_init;  // nullable: the reference's warm duals [B][52N] = [lam_x | lam_a]
   const float* mu;      // nullable: per-instance friction coefficient [B] (NULL: KParams::mu)
   const float* fz_min;  // nullable: per-instance stance fz floor [B] (NULL: KParams::fz_min)
+  const float* Q;       // nullable: per-instance state-weight diagonal [B][12] (NULL: KParams::Q2 / 2)
+  const float* R;       // nullable: per-instance input-weight diagonal [B][12] (NULL: KParams::R2 / 2)
 };
 struct Outputs {
   float* w;

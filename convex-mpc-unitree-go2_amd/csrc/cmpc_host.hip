@@ -308,7 +308,7 @@ int cmpc_solve(cmpc_plan* pl, int64_t B, const float* Ad, const float* Bd, const
                const float* x0, const float* xref, const uint8_t* contact, float* w_out,
                int32_t* status, int32_t* iters, void* stream) {
   return solve_checked(pl, B,
-                       cmpc::Inputs{Ad, Bd, gd, x0, xref, contact, nullptr, nullptr, nullptr, nullptr, nullptr},
+                       cmpc::Inputs{Ad, Bd, gd, x0, xref, contact, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
                        cmpc::Outputs{w_out, status, iters, nullptr, nullptr, nullptr}, stream, "cmpc_solve");
 }
 
@@ -317,7 +317,7 @@ int cmpc_solve_warm(cmpc_plan* pl, int64_t B, const float* Ad, const float* Bd,
                     const uint8_t* contact, const float* w_init, const float* y_init,
                     float* w_out, float* y_out, int32_t* status, int32_t* iters, void* stream) {
   return solve_checked(pl, B,
-                       cmpc::Inputs{Ad, Bd, gd, x0, xref, contact, w_init, y_init, nullptr, nullptr, nullptr},
+                       cmpc::Inputs{Ad, Bd, gd, x0, xref, contact, w_init, y_init, nullptr, nullptr, nullptr, nullptr, nullptr},
                        cmpc::Outputs{w_out, status, iters, y_out, nullptr, nullptr}, stream,
                        "cmpc_solve_warm");
 }
@@ -327,7 +327,7 @@ int cmpc_solve_ref(cmpc_plan* pl, int64_t B, const float* Ad, const float* Bd, c
                    const float* w_init, const float* lam_init, float* w_out, float* lam_out,
                    int32_t* status, int32_t* iters, void* stream) {
   return solve_checked(pl, B,
-                       cmpc::Inputs{Ad, Bd, gd, x0, xref, contact, w_init, nullptr, lam_init, nullptr, nullptr},
+                       cmpc::Inputs{Ad, Bd, gd, x0, xref, contact, w_init, nullptr, lam_init, nullptr, nullptr, nullptr, nullptr},
                        cmpc::Outputs{w_out, status, iters, nullptr, lam_out, nullptr}, stream,
                        "cmpc_solve_ref");
 }
@@ -346,7 +346,7 @@ int cmpc_solve_io_run(cmpc_plan* pl, int64_t B, const cmpc_solve_io* io, void* s
                                 "lam_init / lam_out (the reference's multipliers) are exclusive");
   return solve_checked(pl, B,
                        cmpc::Inputs{a.Ad, a.Bd, a.gd, a.x0, a.xref, a.contact, a.w_init, a.y_init,
-                                    a.lam_init, a.mu, a.fz_min},
+                                    a.lam_init, a.mu, a.fz_min, a.Q, a.R},
                        cmpc::Outputs{a.w_out, a.status, a.iters, a.y_out, a.lam_out, nullptr}, stream,
                        "cmpc_solve_io_run");
 }

@@ -332,7 +332,8 @@ struct Smem {
   float D[kMaxP];                  // d_k  (error-coordinate affine term)
   float Dt[kMaxP];                 // d~_k (d_k + B_k t0_k in the polish basis)
   float A[144];
-  float Q2[12];                    // KParams copies (indexed at run time -> keep out of kernarg)
+  float Q2[12];                    // KParams copies (indexed at run time -> keep out of kernarg),
+                                   // or the instance's own 2Q / 2R (Inputs::Q / R, solve_instance)
   float R2[12];
   int par[NC];                     // param -> step k
   int off[kMaxN + 1];              // first param of step k
@@ -1777,18 +1778,18 @@ __device__ __forceinline__ bool polish_check(Smem<NC>& s, const KParams& P, cons
 // The certified force error of the held faces at the point polish_check accepted (its per-triple
 // |c_t|^2 and the force scale are in s.r): within kCertFace of the force scale?  Uniform.
 template <int NC>
-__device__ __forceinline__ bool certified_faces(Smem<NC>& s, const KParams& P) {
+__device__ __forceinline__ bool certified_faces(Smem<NC>& s, float r2_min) {
   const int lane = opaque_lane();
   WSYNC();
   const float c2 = wave_sum(s.r[lane]);
-  return uniformf(sqrtf(c2)) <= kCertFace * P.r2_min * uniformf(s.r[64]);
+  return uniformf(sqrtf(c2)) <= kCertFace * r2_min * uniformf(s.r[64]);
 }
 
 #ifdef CMPC_DIAG_GRES
 // diagnostic build: at an accepted point, |grad|_2 (the gradient at the final refinement point,
 // s.g over the nact params) and |c|_2, both over min 2R x the force scale (force-error units)
 template <int NC>
-__device__ __forceinline__ void diag_gres(Smem<NC>& s, const KParams& P, int nact, float& gm,
+__device__ __forceinline__ void diag_gres(Smem<NC>& s, float r2_min, int nact, float& gm,
                                           float& cm, float& us) {
   const int lane = opaque_lane();
   WSYNC();
@@ -1797,8 +1798,8 @@ __device__ __forceinline__ void diag_gres(Smem<NC>& s, const KParams& P, int nac
   g2 = wave_sum(g2);
   const float c2 = wave_sum(s.r[lane]);
   us = uniformf(s.r[64]);
-  gm = uniformf(sqrtf(g2)) / (P.r2_min * us);
-  cm = uniformf(sqrtf(c2)) / (P.r2_min * us);
+  gm = uniformf(sqrtf(g2)) / (r2_min * us);
+  cm = uniformf(sqrtf(c2)) / (r2_min * us);
 }
 #endif
 
@@ -2015,6 +2016,10 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
   const int N = P.N;
   const int NP = 12 * N;
   const Terrain T = instance_terrain(P, in, b);
+  // per-instance weights (Inputs::Q / R): valid?  and the strong-convexity modulus min_i R2[i]
+  // of this instance; both wave-uniform scalars like T, set with the staging loads below
+  bool weights_ok = true;
+  float r2_min = P.r2_min;
 #if defined(CMPC_POISON_LDS)  // diagnostic: NaN into the float scratch before every instance
   if constexpr (W == 1) {
     const float qn = __int_as_float(0x7fc00000);
@@ -2052,6 +2057,24 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
       rv[i] = (e < 12) ? x0b[e] : (e < 12 * (N + 1)) ? xrb[e - 12] : 0.f;
     }
     const float gv = (lane < 12) ? gdb[lane] : 0.f;
+    // this instance's cost weights (Inputs::Q / R) over the wave's copies of the plan's
+    // (drain_bin), which stay where the pointer is NULL.  Every reader of s.Q2 / s.R2 comes
+    // after the WSYNC below; in team mode the helpers read them only inside a FACTOR command,
+    // before that command's sweep barriers, which the leader passes with them: like s.A they
+    // are rewritten here while the helpers wait at the next command's barrier.  An invalid row
+    // (cmpc_plan_create's test of the constants; false also for NaN) takes the all-swing path
+    // below, whose outputs depend on neither: finite stand-ins (Q2 = 0, R2 = 2) are stored.
+    if (in.Q || in.R) {  // (uniform)
+      const float q = (in.Q && lane < 12) ? in.Q[b * 12 + lane] : 0.f;
+      const float r = (in.R && lane < 12) ? in.R[b * 12 + lane] : 1.f;
+      weights_ok = __any(!(q >= 0.f && isfinite(q) && r > 0.f && isfinite(r))) == 0;
+      if (lane < 12) {
+        if (in.Q) s.Q2[lane] = weights_ok ? 2.f * q : 0.f;
+        if (in.R) s.R2[lane] = weights_ok ? 2.f * r : 2.f;
+      }
+      if (in.R)
+        r2_min = weights_ok ? uniformf(-wave_max((lane < 12) ? -2.f * r : -INFINITY)) : 2.f;
+    }
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       const int e = lane + 64 * i;
@@ -2061,10 +2084,10 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
     for (int i = 0; i < 4; ++i) s.G[lane + 64 * i] = rv[i];
     if (lane < 12) s.G[256 + lane] = gv;
   }
-  // stance triples in (k, leg) order; lane = 4k + leg.  An instance whose mu / fz_min entry is
-  // invalid has no feasible set to solve on: it takes the all-swing path (zero forces, X = the
-  // rollout) and returns status -10
-  const bool stc = (lane < 4 * N && terrain_valid(T)) ? (ctb[(lane & 3) * N + (lane >> 2)] != 0) : false;
+  // stance triples in (k, leg) order; lane = 4k + leg.  An instance whose mu / fz_min entry or
+  // Q / R row is invalid has no problem to solve: it takes the all-swing path (zero forces,
+  // X = the rollout) and returns status -10
+  const bool stc = (lane < 4 * N && terrain_valid(T) && weights_ok) ? (ctb[(lane & 3) * N + (lane >> 2)] != 0) : false;
   const int pos = wave_excl_scan4(stc ? 1 : 0);
   const int ntri = wave_total4(stc ? 1 : 0);
   if (stc) s.tri[pos] = lane;
@@ -2333,9 +2356,9 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
       // multipliers); a point that misses the bound is returned as status 2
       if (ok && !dd_stall) {
 #ifdef CMPC_DIAG_GRES
-        diag_gres<NC>(s, P, nact, dg_gm, dg_cm, dg_us);
+        diag_gres<NC>(s, r2_min, nact, dg_gm, dg_cm, dg_us);
 #endif
-        const bool cert = !uniform(s.nil) || certified_faces<NC>(s, P);
+        const bool cert = !uniform(s.nil) || certified_faces<NC>(s, r2_min);
         if (!cert && out.stats != nullptr && lane == 0) atomicAdd(&out.stats[1], 1ull);
 #ifdef CMPC_DIAG_COUNTS
         if (!cert) dg_flags |= 2;
@@ -2402,9 +2425,9 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
       }
       if (loose) {  // the session ends on a set within the loose tolerance: accept it
 #ifdef CMPC_DIAG_GRES
-        diag_gres<NC>(s, P, nact, dg_gm, dg_cm, dg_us);
+        diag_gres<NC>(s, r2_min, nact, dg_gm, dg_cm, dg_us);
 #endif
-        const bool certok = certified_faces<NC>(s, P);
+        const bool certok = certified_faces<NC>(s, r2_min);
         const int l = opaque_lane();
         WSYNC();
         if (l < ntri) {  // (projected onto the pyramid: the loose check admits 5x polish_tol)
@@ -2663,7 +2686,7 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
     wb[o] = xv;
     wb[NP + o] = uv;
   }
-  if (__any(bad) || !terrain_valid(T)) status = -10;
+  if (__any(bad) || !terrain_valid(T) || !weights_ok) status = -10;
 #ifdef CMPC_DIAG_COUNTS  // diagnostic build: w[0..7] = cycles and factorizations at failed sessions 1..4
   if (lane < 4) wb[lane] = dg_fail_t[lane];
   else if (lane < 8) wb[lane] = (float)dg_fail_f[lane - 4];
@@ -2685,7 +2708,10 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
       yb[o] = (t >= 0) ? sg * yf[3 * t + a] : 0.f;
     }
   }
-  if (out.lam) {  // the reference's multipliers at the returned point (CasADi convention)
+  if (out.lam && !weights_ok) {  // an invalid Q / R row has no multipliers: a zero row
+    float* lb = out.lam + b * (int64_t)(52 * N);
+    for (int o = lane; o < 52 * N; o += 64) lb[o] = 0.f;
+  } else if (out.lam) {  // the reference's multipliers at the returned point (CasADi convention)
     // L holds lambda_k = the adjoint at the returned forces (the last gradient call), and
     // lam_eq[k] = -lambda_k (stationarity of x_{k+1}).  Lane 4k + leg: s = 2R u + Bd_k' lambda_k
     // on its three forces, then the friction-row / bound multipliers of its faces.
@@ -2766,7 +2792,9 @@ __device__ __forceinline__ void drain_bin(Smem<NC>& s, const KParams& P, const I
                                           int* seq = nullptr) {
   const int lane = opaque_lane();
   WSYNC();
-  if (lane < 12) {  // KParams copies (each bin's Smem layout places them differently)
+  // KParams copies (each bin's Smem layout places them differently); solve_instance overwrites
+  // them per instance where Inputs::Q / R are given
+  if (lane < 12) {
     s.Q2[lane] = P.Q2[lane];
     s.R2[lane] = P.R2[lane];
   }

@@ -48,7 +48,8 @@
  *                                       point that misses the certified bound (returned, but not
  *                                       verified to 1e-4),
  *                                     -2 max iterations, -10 numerical failure or an invalid
- *                                       per-instance mu / fz_min entry (cmpc_solve_io)
+ *                                       per-instance mu / fz_min entry or Q / R row
+ *                                       (cmpc_solve_io)
  *   iters   [B]                int32  ADMM iterations taken
  *
  * Threading: one plan per host thread / stream.  cmpc_solve is asynchronous on `stream`
@@ -185,6 +186,17 @@ int cmpc_solve_ref(cmpc_plan* plan, int64_t B, const float* Ad, const float* Bd,
  * never fails the call: that instance returns status -10 with zero forces and X = the rollout
  * of zero forces (the path an instance with no stance leg takes), its y_out row is zero, and
  * every other instance of the batch is solved as if the entry were valid.
+ * Per-instance cost weights, the same way:
+ *   Q       [B][12]  fp32  nullable; the state-weight diagonal of instance b (NULL: params.Q)
+ *   R       [B][12]  fp32  nullable; its input-weight diagonal (NULL: params.R)
+ * in the order of params.Q / params.R.  The kernels read the rows when they run (a captured
+ * graph sees values written in place since), and NULL, or rows filled with the plan's
+ * constants, compute bit for bit what the plan's constants compute; either array alone may be
+ * given.  A row is invalid by the tests cmpc_plan_create applies to the constants: any Q entry
+ * negative or not finite, any R entry <= 0 or not finite.  An invalid row is treated as an
+ * invalid terrain entry is: status -10, zero forces, X = the rollout of zero forces, a zero
+ * y_out / lam_out row, and the rest of the batch solved normally.  The status-1 certificate
+ * uses the instance's own strong-convexity modulus min_i 2 R[b][i].
  * `size` is the caller's sizeof of the struct: fields past it are read as NULL, so the struct
  * can grow at its end without an ABI bump.  The inputs Ad..contact and the outputs w_out,
  * status, iters are required; w_init, y_init / y_out and lam_init / lam_out are as for
@@ -203,6 +215,9 @@ typedef struct cmpc_solve_io {
   /* outputs */
   float *w_out, *y_out, *lam_out;          /* y_out, lam_out nullable */
   int32_t *status, *iters;
+  /* appended after the first release of this struct (a smaller `size` reads them as NULL) */
+  const float* Q;           /* [B][12] nullable */
+  const float* R;           /* [B][12] nullable */
 } cmpc_solve_io;
 
 int cmpc_solve_io_run(cmpc_plan* plan, int64_t B, const cmpc_solve_io* io, void* stream);
