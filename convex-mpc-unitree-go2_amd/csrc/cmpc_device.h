@@ -26,30 +26,30 @@ struct KParams {
 
 // Device pointers of one cmpc_solve call (layouts: include/cmpc.h).
 struct Inputs {
-  const float* Ad;
-  const float* Bd;
-  const float* gd;
-  const float* x0;
-  const float* xref;
-  const uint8_t* contact;
-  const float* w_init;  // nullable: primal warm start, cmpc_solve_warm's w layout
-  const float* y_init;  // nullable: dual warm start [B][12N] (force layout)
-  const float* lam_init;  // nullable: the reference's warm duals [B][52N] = [lam_x | lam_a]
-  const float* mu;      // nullable: per-instance friction coefficient [B] (NULL: KParams::mu)
-  const float* fz_min;  // nullable: per-instance stance fz floor [B] (NULL: KParams::fz_min)
-  const float* Q;       // nullable: per-instance state-weight diagonal [B][12] (NULL: KParams::Q2 / 2)
-  const float* R;       // nullable: per-instance input-weight diagonal [B][12] (NULL: KParams::R2 / 2)
+  const float* Ad = nullptr;
+  const float* Bd = nullptr;
+  const float* gd = nullptr;
+  const float* x0 = nullptr;
+  const float* xref = nullptr;
+  const uint8_t* contact = nullptr;
+  const float* w_init = nullptr;  // nullable: primal warm start, cmpc_solve_warm's w layout
+  const float* y_init = nullptr;  // nullable: dual warm start [B][12N] (force layout)
+  const float* lam_init = nullptr;  // nullable: the reference's warm duals [B][52N] = [lam_x | lam_a]
+  const float* mu = nullptr;      // nullable: per-instance friction coefficient [B] (NULL: KParams::mu)
+  const float* fz_min = nullptr;  // nullable: per-instance stance fz floor [B] (NULL: KParams::fz_min)
+  const float* Q = nullptr;       // nullable: per-instance state-weight diagonal [B][12] (NULL: KParams::Q2 / 2)
+  const float* R = nullptr;       // nullable: per-instance input-weight diagonal [B][12] (NULL: KParams::R2 / 2)
 };
 struct Outputs {
-  float* w;
-  int32_t* status;
-  int32_t* iters;
-  float* y;             // nullable: the dual at the returned forces [B][12N]
-  float* lam;           // nullable: the reference's multipliers [B][52N] = [lam_x | lam_a]
+  float* w = nullptr;
+  int32_t* status = nullptr;
+  int32_t* iters = nullptr;
+  float* y = nullptr;             // nullable: the dual at the returned forces [B][12N]
+  float* lam = nullptr;           // nullable: the reference's multipliers [B][52N] = [lam_x | lam_a]
   // nullable: per-plan cumulative counters (cmpc_plan_stats): [0] loose acceptances, [1] status 2
   // because the certified face bound was missed, [2] checks on a stalled downdated refinement
   // redone on a fresh factorization
-  unsigned long long* stats;
+  unsigned long long* stats = nullptr;
 };
 
 // Free-variable capacities of the LDS bins (3 forces per stance (step, leg)).  Solve kernels

@@ -304,32 +304,57 @@ static int solve_checked(cmpc_plan* pl, int64_t B, const cmpc::Inputs& in, cmpc:
   return solve_impl(pl, B, in, out, stream);
 }
 
+// The arrays every solve entry takes; the entries set the optional fields they pass by name
+// (the rest stay NULL).
+static cmpc::Inputs problem_inputs(const float* Ad, const float* Bd, const float* gd,
+                                   const float* x0, const float* xref, const uint8_t* contact) {
+  cmpc::Inputs in;
+  in.Ad = Ad;
+  in.Bd = Bd;
+  in.gd = gd;
+  in.x0 = x0;
+  in.xref = xref;
+  in.contact = contact;
+  return in;
+}
+
+static cmpc::Outputs solve_outputs(float* w_out, int32_t* status, int32_t* iters) {
+  cmpc::Outputs out;
+  out.w = w_out;
+  out.status = status;
+  out.iters = iters;
+  return out;
+}
+
 int cmpc_solve(cmpc_plan* pl, int64_t B, const float* Ad, const float* Bd, const float* gd,
                const float* x0, const float* xref, const uint8_t* contact, float* w_out,
                int32_t* status, int32_t* iters, void* stream) {
-  return solve_checked(pl, B,
-                       cmpc::Inputs{Ad, Bd, gd, x0, xref, contact, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
-                       cmpc::Outputs{w_out, status, iters, nullptr, nullptr, nullptr}, stream, "cmpc_solve");
+  return solve_checked(pl, B, problem_inputs(Ad, Bd, gd, x0, xref, contact),
+                       solve_outputs(w_out, status, iters), stream, "cmpc_solve");
 }
 
 int cmpc_solve_warm(cmpc_plan* pl, int64_t B, const float* Ad, const float* Bd,
                     const float* gd, const float* x0, const float* xref,
                     const uint8_t* contact, const float* w_init, const float* y_init,
                     float* w_out, float* y_out, int32_t* status, int32_t* iters, void* stream) {
-  return solve_checked(pl, B,
-                       cmpc::Inputs{Ad, Bd, gd, x0, xref, contact, w_init, y_init, nullptr, nullptr, nullptr, nullptr, nullptr},
-                       cmpc::Outputs{w_out, status, iters, y_out, nullptr, nullptr}, stream,
-                       "cmpc_solve_warm");
+  cmpc::Inputs in = problem_inputs(Ad, Bd, gd, x0, xref, contact);
+  in.w_init = w_init;
+  in.y_init = y_init;
+  cmpc::Outputs out = solve_outputs(w_out, status, iters);
+  out.y = y_out;
+  return solve_checked(pl, B, in, out, stream, "cmpc_solve_warm");
 }
 
 int cmpc_solve_ref(cmpc_plan* pl, int64_t B, const float* Ad, const float* Bd, const float* gd,
                    const float* x0, const float* xref, const uint8_t* contact,
                    const float* w_init, const float* lam_init, float* w_out, float* lam_out,
                    int32_t* status, int32_t* iters, void* stream) {
-  return solve_checked(pl, B,
-                       cmpc::Inputs{Ad, Bd, gd, x0, xref, contact, w_init, nullptr, lam_init, nullptr, nullptr, nullptr, nullptr},
-                       cmpc::Outputs{w_out, status, iters, nullptr, lam_out, nullptr}, stream,
-                       "cmpc_solve_ref");
+  cmpc::Inputs in = problem_inputs(Ad, Bd, gd, x0, xref, contact);
+  in.w_init = w_init;
+  in.lam_init = lam_init;
+  cmpc::Outputs out = solve_outputs(w_out, status, iters);
+  out.lam = lam_out;
+  return solve_checked(pl, B, in, out, stream, "cmpc_solve_ref");
 }
 
 int cmpc_solve_io_run(cmpc_plan* pl, int64_t B, const cmpc_solve_io* io, void* stream) {
@@ -344,11 +369,48 @@ int cmpc_solve_io_run(cmpc_plan* pl, int64_t B, const cmpc_solve_io* io, void* s
   if ((a.y_init || a.y_out) && (a.lam_init || a.lam_out))
     return fail(CMPC_E_INVALID, "cmpc_solve_io_run: y_init / y_out (this solver's dual) and "
                                 "lam_init / lam_out (the reference's multipliers) are exclusive");
-  return solve_checked(pl, B,
-                       cmpc::Inputs{a.Ad, a.Bd, a.gd, a.x0, a.xref, a.contact, a.w_init, a.y_init,
-                                    a.lam_init, a.mu, a.fz_min, a.Q, a.R},
-                       cmpc::Outputs{a.w_out, a.status, a.iters, a.y_out, a.lam_out, nullptr}, stream,
-                       "cmpc_solve_io_run");
+  cmpc::Inputs in = problem_inputs(a.Ad, a.Bd, a.gd, a.x0, a.xref, a.contact);
+  in.w_init = a.w_init;
+  in.y_init = a.y_init;
+  in.lam_init = a.lam_init;
+  in.mu = a.mu;
+  in.fz_min = a.fz_min;
+  in.Q = a.Q;
+  in.R = a.R;
+  cmpc::Outputs out = solve_outputs(a.w_out, a.status, a.iters);
+  out.y = a.y_out;
+  out.lam = a.lam_out;
+  return solve_checked(pl, B, in, out, stream, "cmpc_solve_io_run");
+}
+
+// The event pair around one solve-kernel launch (cmpc_plan_timing_read).  timing_begin takes a
+// pair from the pool (or creates one) and records `a` on stream s; timing_end records `b` and
+// files the pair as pending.  A launch that is not recorded (timing off, `timed` false, or the
+// record is full) leaves rec.a null, and timing_end then does nothing.
+static int timing_begin(cmpc_plan* pl, int group, hipStream_t s, bool timed, cmpc_plan::Rec& rec) {
+  hipError_t e;
+  rec = cmpc_plan::Rec{nullptr, nullptr, group};
+  if (!(timed && pl->timing && pl->recs.size() < 4096 * kNumGroups)) return CMPC_OK;
+  if (!pl->pool.empty()) {
+    rec = pl->pool.back();
+    pl->pool.pop_back();
+    rec.group = group;
+  } else {
+    cmpc_plan::Rec fresh{nullptr, nullptr, group};
+    if ((e = hipEventCreate(&fresh.a)) != hipSuccess) return hip_fail(e, "hipEventCreate");
+    if ((e = hipEventCreate(&fresh.b)) != hipSuccess) return hip_fail(e, "hipEventCreate");
+    rec = fresh;
+  }
+  if ((e = hipEventRecord(rec.a, s)) != hipSuccess) return hip_fail(e, "hipEventRecord");
+  return CMPC_OK;
+}
+
+static int timing_end(cmpc_plan* pl, hipStream_t s, const cmpc_plan::Rec& rec) {
+  if (!rec.a) return CMPC_OK;
+  const hipError_t e = hipEventRecord(rec.b, s);
+  if (e != hipSuccess) return hip_fail(e, "hipEventRecord");
+  pl->recs.push_back(rec);
+  return CMPC_OK;
 }
 
 // group k's persistent kernel with g waves whose park slabs start at wave w0 of the group's
@@ -357,33 +419,18 @@ int cmpc_solve_io_run(cmpc_plan* pl, int64_t B, const cmpc_solve_io* io, void* s
 static int record_launch(cmpc_plan* pl, int k, hipStream_t s, const cmpc::KParams& kp,
                          const cmpc::Inputs& in, const cmpc::Outputs& out, unsigned g,
                          unsigned w0 = 0, bool timed = true) {
-  hipError_t e;
-  cmpc_plan::Rec rec{nullptr, nullptr, k};
-  const bool rec_this = timed && pl->timing && pl->recs.size() < 4096 * kNumGroups;
-  if (rec_this) {
-    if (!pl->pool.empty()) {
-      rec = pl->pool.back();
-      pl->pool.pop_back();
-      rec.group = k;
-    } else {
-      if ((e = hipEventCreate(&rec.a)) != hipSuccess) return hip_fail(e, "hipEventCreate");
-      if ((e = hipEventCreate(&rec.b)) != hipSuccess) return hip_fail(e, "hipEventCreate");
-    }
-    if ((e = hipEventRecord(rec.a, s)) != hipSuccess) return hip_fail(e, "hipEventRecord");
-  }
+  cmpc_plan::Rec rec;
+  int rc = timing_begin(pl, k, s, timed, rec);
+  if (rc != CMPC_OK) return rc;
   const int qa = group_first_bin(k);
   hipLaunchKernelGGL(group_fn(k), dim3(g), dim3(64), 0, s, kp, in, out,
                      pl->d_lists + (size_t)qa * pl->p.max_batch,
                      pl->d_lists + (size_t)(qa - 1) * pl->p.max_batch, pl->d_counters,
                      pl->d_counters + cmpc::kNumBins, qa,
                      pl->d_work + pl->work_off[k] + (size_t)w0 * pl->slab[k], pl->slab[k]);
-  e = hipGetLastError();
+  const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "solve_group_kernel launch");
-  if (rec_this) {
-    if ((e = hipEventRecord(rec.b, s)) != hipSuccess) return hip_fail(e, "hipEventRecord");
-    pl->recs.push_back(rec);
-  }
-  return CMPC_OK;
+  return timing_end(pl, s, rec);
 }
 
 static int64_t heavy_first_batch(const cmpc_plan* pl) {
@@ -411,20 +458,9 @@ static bool team_one_per_cu(const cmpc_plan* pl, int64_t B) {
 // team mode: one launch for every bin; timed as solve kernel 0 (kernel 1 records no call)
 static int record_team_launch(cmpc_plan* pl, hipStream_t s, const cmpc::KParams& kp,
                               const cmpc::Inputs& in, const cmpc::Outputs& out, int64_t B) {
-  hipError_t e;
-  cmpc_plan::Rec rec{nullptr, nullptr, 0};
-  const bool rec_this = pl->timing && pl->recs.size() < 4096 * kNumGroups;
-  if (rec_this) {
-    if (!pl->pool.empty()) {
-      rec = pl->pool.back();
-      pl->pool.pop_back();
-      rec.group = 0;
-    } else {
-      if ((e = hipEventCreate(&rec.a)) != hipSuccess) return hip_fail(e, "hipEventCreate");
-      if ((e = hipEventCreate(&rec.b)) != hipSuccess) return hip_fail(e, "hipEventCreate");
-    }
-    if ((e = hipEventRecord(rec.a, s)) != hipSuccess) return hip_fail(e, "hipEventRecord");
-  }
+  cmpc_plan::Rec rec;
+  int rc = timing_begin(pl, 0, s, true, rec);
+  if (rc != CMPC_OK) return rc;
   // one QP per CU: the one-workgroup-per-CU image (512 registers per lane, no spills)
   if (team_one_per_cu(pl, B)) {
     const unsigned g = (unsigned)(pl->team_grid1 < B ? pl->team_grid1 : B);
@@ -437,13 +473,9 @@ static int record_team_launch(cmpc_plan* pl, hipStream_t s, const cmpc::KParams&
                        s, kp, in, out, pl->d_lists, (int64_t)pl->p.max_batch, pl->d_counters,
                        pl->d_counters + cmpc::kNumBins, pl->d_work, pl->team_slab);
   }
-  e = hipGetLastError();
+  const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "solve_team_kernel launch");
-  if (rec_this) {
-    if ((e = hipEventRecord(rec.b, s)) != hipSuccess) return hip_fail(e, "hipEventRecord");
-    pl->recs.push_back(rec);
-  }
-  return CMPC_OK;
+  return timing_end(pl, s, rec);
 }
 
 static int solve_impl(cmpc_plan* pl, int64_t B, const cmpc::Inputs& in, const cmpc::Outputs& out,

@@ -170,24 +170,9 @@ __device__ __forceinline__ int opaque_lane() {
 // attempts, 10 instances, 11 ADMM iterations, 12 gradient calls, 13 symv calls, 29 downdated
 // repairs, 30 downdated faces (16-27: team-mode phases, cmpc_team.hip).
 // ------------------------------------------------------------------------------------------
-// diagnostic build only (-DCMPC_TRACE=id, or -DCMPC_TRACE_IDS=id,id,... to trace several
-// instances inside a full batch): device printf of one instance's ADMM iterations, polish
-// sessions, refinements and KKT checks, every line prefixed with the instance index
-#if defined(CMPC_TRACE_IDS) && !defined(CMPC_TRACE)
-#define CMPC_TRACE (-1)
-#endif
-#ifdef CMPC_TRACE
-__device__ __forceinline__ bool trace_on(int64_t b) {
-#ifdef CMPC_TRACE_IDS
-  constexpr int64_t ids[] = {CMPC_TRACE_IDS};
-  bool on = false;
-  for (int64_t i : ids) on |= (b == i);
-  return on;
-#else
-  return b == CMPC_TRACE;
-#endif
-}
-#endif
+// every other diagnostic build (trace, counts, gres, times, poison): the Diag hooks and the
+// trace macros of cmpc_diag.h
+#include "cmpc_diag.h"
 #ifdef CMPC_STAMPS
 __device__ unsigned long long g_stamps[32];
 // (fenced: outstanding memory and LDS traffic completes, no code moves across a stamp; totals
@@ -333,7 +318,7 @@ struct Smem {
   float Dt[kMaxP];                 // d~_k (d_k + B_k t0_k in the polish basis)
   float A[144];
   float Q2[12];                    // KParams copies (indexed at run time -> keep out of kernarg),
-                                   // or the instance's own 2Q / 2R (Inputs::Q / R, solve_instance)
+                                   // or the instance's own 2Q / 2R (Inputs::Q / R, stage_instance)
   float R2[12];
   int par[NC];                     // param -> step k
   int off[kMaxN + 1];              // first param of step k
@@ -1614,20 +1599,30 @@ __device__ __forceinline__ int polish_setup(Smem<NC>& s, const KParams& P, const
   return nr;
 }
 
+// What polish_check found (all wave-uniform).
+struct PolishCheck {
+  bool ok;         // every KKT condition holds and the refinement step is within tolerance
+  bool changed;    // the repaired face set (s.tcnt) differs from the checked one
+  bool loose;      // every relative KKT violation (multipliers against the gradient scale, forces
+                   // against the force scale) is within kLooseTol x polish_tol
+  bool converged;  // the refinement step is within polish_tol x the force scale
+  bool amb;        // a held face's multiplier lies within the ambiguity band of zero
+  bool decisive;   // a violation outside that band fails the check
+  float vworst;    // the largest relative violation
+};
+
 // Polish check after refinement (E, L at the final v in LDS): KKT conditions per triple
 // (lane t = triple t, its params from s.fpk).  On success the triple's force is written over
 // its ADMM primal s.x[3t .. 3t+2]; the repaired face code of a failing triple is left in
-// s.tcnt and `changed` says whether any face changed.  `loose` says whether every relative KKT
-// violation (multipliers against the gradient scale, forces against the force scale) is within
-// kLooseTol x polish_tol; the candidate forces are left in s.dl[3t .. 3t+2] for that case.
+// s.tcnt and `changed` says whether any face changed.  For a loose acceptance the candidate
+// forces are left in s.dl[3t .. 3t+2].
 // top > 0: the repair changes only the `top` triples with the largest relative violation (the
-// others keep their faces).
+// others keep their faces).  tr >= 0: trace the triples near a bound (cmpc_diag.h trace_id).
 template <int NC>
-__device__ __forceinline__ bool polish_check(Smem<NC>& s, const KParams& P, const Terrain& T,
-                                             const float* __restrict__ Bg, int ntri, float step,
-                                             bool& changed, bool& loose, bool& converged,
-                                             bool& amb, bool& decisive, float& vworst,
-                                             int top = 0, int tr = -1) {
+__device__ __forceinline__ PolishCheck polish_check(Smem<NC>& s, const KParams& P,
+                                                    const Terrain& T, const float* __restrict__ Bg,
+                                                    int ntri, float step, int top = 0,
+                                                    int tr = -1) {
   const int lane = opaque_lane();
   const float mu = T.mu, fzmin = T.fz_min;
   float fx = 0.f, fy = 0.f, fz = 0.f;
@@ -1707,11 +1702,9 @@ __device__ __forceinline__ bool polish_check(Smem<NC>& s, const KParams& P, cons
     v = fmaxf(v, fmaxf(sx ? 0.f : (fabsf(fx) - mu * fz) * iu, sy ? 0.f : (fabsf(fy) - mu * fz) * iu));
     v = fmaxf(v, zl ? 0.f : (fzmin - fz) * iu);
     const bool fin = isfinite(fx) && isfinite(fy) && isfinite(fz);
-#ifdef CMPC_TRACE
-    if (tr >= 0 && (v > 0.f || (sx && lx < tfx) || (sy && ly < tfy) || (zl && l0 < tfz)))
-      printf("[%d]       tri %d k %d leg %d code %d f %g %g %g  l %g %g %g  tol %g %g %g  v %g\n", tr,
-             lane, k, leg, code, fx, fy, fz, lx, ly, l0, tfx, tfy, tfz, v);
-#endif
+    TRACE_IF(tr >= 0 && (v > 0.f || (sx && lx < tfx) || (sy && ly < tfy) || (zl && l0 < tfz)),
+             "[%d]       tri %d k %d leg %d code %d f %g %g %g  l %g %g %g  tol %g %g %g  v %g\n",
+             tr, lane, k, leg, code, fx, fy, fz, lx, ly, l0, tfx, tfy, tfz, v);
     lok = fin && v <= kLooseTol * P.polish_tol;
     // (precise: a loose acceptance also bounds the force error of every face it holds)
     if (prec)
@@ -1752,15 +1745,17 @@ __device__ __forceinline__ bool polish_check(Smem<NC>& s, const KParams& P, cons
     if (cand && !sel) nc = code;
   }
   if (owns) s.tcnt[lane] = nc;  // repaired code (copied into s.code by the caller if used)
-  changed = __any(owns && nc != code) != 0;
-  amb = __any(am) != 0;
+  PolishCheck res;
+  res.changed = __any(owns && nc != code) != 0;
+  res.amb = __any(am) != 0;
   // (only multipliers within the ambiguity band fail: the decision rests on the point's accuracy)
-  decisive = __any(dec) != 0;
-  vworst = wave_max((owns && isfinite(v)) ? v : (owns ? 1e30f : 0.f));
+  res.decisive = __any(dec) != 0;
+  res.vworst = wave_max((owns && isfinite(v)) ? v : (owns ? 1e30f : 0.f));
   const bool step_ok = step <= P.polish_tol * us;
-  converged = step_ok;
-  loose = (__all(lok) != 0) && step_ok;
+  res.converged = step_ok;
+  res.loose = (__all(lok) != 0) && step_ok;
   const bool all_ok = (__all(ok) != 0) && step_ok;
+  res.ok = all_ok;
   if (all_ok && owns) {
     // onto the pyramid exactly: the check admits violations up to polish_tol x the force scale
     // (~2e-3 N), the reference's bounds take none (a move of at most that, far inside the 1e-4
@@ -1771,7 +1766,7 @@ __device__ __forceinline__ bool polish_check(Smem<NC>& s, const KParams& P, cons
     s.x[3 * lane + 1] = py;
     s.x[3 * lane + 2] = pz;
   }
-  return all_ok;
+  return res;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1784,24 +1779,6 @@ __device__ __forceinline__ bool certified_faces(Smem<NC>& s, float r2_min) {
   const float c2 = wave_sum(s.r[lane]);
   return uniformf(sqrtf(c2)) <= kCertFace * r2_min * uniformf(s.r[64]);
 }
-
-#ifdef CMPC_DIAG_GRES
-// diagnostic build: at an accepted point, |grad|_2 (the gradient at the final refinement point,
-// s.g over the nact params) and |c|_2, both over min 2R x the force scale (force-error units)
-template <int NC>
-__device__ __forceinline__ void diag_gres(Smem<NC>& s, float r2_min, int nact, float& gm,
-                                          float& cm, float& us) {
-  const int lane = opaque_lane();
-  WSYNC();
-  float g2 = 0.f;
-  for (int p = lane; p < nact; p += 64) g2 = fmaf(s.g[p], s.g[p], g2);
-  g2 = wave_sum(g2);
-  const float c2 = wave_sum(s.r[lane]);
-  us = uniformf(s.r[64]);
-  gm = uniformf(sqrtf(g2)) / (r2_min * us);
-  cm = uniformf(sqrtf(c2)) / (r2_min * us);
-}
-#endif
 
 // Face downdates (round 4).  A repair that only ADDS faces to the current face set keeps the
 // basis and the inverse M of the last factorization: each added face is an equality a'v = c on
@@ -2004,44 +1981,92 @@ __device__ __forceinline__ bool tried_before(Smem<NC>& s, int ntri, int ntried) 
   return hit;
 }
 
-template <int NC, int W>
-__device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, int64_t b,
-                                               const Inputs& in, const Outputs& out,
-                                               float* __restrict__ park, TeamSmem<NC, W>* ts,
-                                               int* seq) {
-  // W = 1: the whole lower triangle in this wave's registers; W > 1: this wave's team slots
-  f4 M[TeamCfg<NC, W>::SLOTS];
-  static_assert(W > 1 || TeamCfg<NC, W>::SLOTS == Cfg<NC>::NTL, "W = 1 holds every tile");
-  const int lane = opaque_lane();
-  const int N = P.N;
-  const int NP = 12 * N;
-  const Terrain T = instance_terrain(P, in, b);
+// ------------------------------------------------------------------------------------------
+// solve_instance and its phases.  The driver (solve_instance, at the end) stages the instance,
+// picks the starting point and then loops: factorize when asked, one polish pass while a
+// session is open (its outcome, a Polish value, selects the state changes), else one ADMM
+// iteration, which may open a session.  The writers of w, y and lam follow the loop.
+// ------------------------------------------------------------------------------------------
+
+// Initial rho per bin: the NC >= 128 bins (33-64 stance triples) converge in fewer iterations
+// from rho0 / 2; their hard instances (a failed polish session) go back to rho0, where they
+// converge as before (NC = 128: cfg1 +6-10 %, cfg2 +1 %; NC >= 160: kRhoLowHeavy; rho0 / 2
+// for the NC = 96 bin too loses 7 % on cfg2)
+template <int NC>
+constexpr bool kRhoLow = (NC == 128) || (kRhoLowHeavy && NC > 128);
+
+// What the instance is: wave-uniform, fixed once stage_instance has run.
+struct Instance {
+  int64_t b;         // index in the batch
+  int N, NP;         // horizon, 12 N
+  Terrain T;         // this instance's mu / fz_min
+  bool weights_ok;   // per-instance weights (Inputs::Q / R): valid?
+  float r2_min;      // the strong-convexity modulus min_i R2[i] of this instance
+  const float* Bg;   // its Bd [N][12][12]
+  const float* xrb;  // its xref [N][12]
+  int ntri, n;       // stance triples, ADMM params (3 ntri)
+  bool nil;          // A = I + N, N^2 = 0: the closed-form condensation
+  const f4* pwc;     // team mode, NC <= 128: the gradient's powers of A (else null)
+  const f4* twc;
+};
+
+// What steers the solve loop: wave-uniform scalars, changed by the phases and by the driver's
+// switch over a polish pass's outcome.
+struct Ctl {
+  int status = -2, iters = 0;
+  bool polished = false;  // a polish pass accepted its point (the forces are in s.x)
+  float rp = 0.f, rd = 0.f, np_ = 0.f, nd = 0.f;  // ADMM residuals and their scales
+  float rho = 0.f;
+  bool rho_low = false;   // still at the bin's reduced initial rho
+  int stable = 0;         // ADMM iterations since the face set last changed
+  bool refactor = false;  // (re)build + invert the matrix for the current basis
+  bool in_polish = false;
+  int nact = 0;           // params of the current basis
+  float shift = 0.f;      // sigma + rho (ADMM) or sigma (polish) on the matrix diagonal
+  int it = 0;
+  int repairs_left = 0;
+  int nadd = 0;           // faces added by downdates since the last factorization
+  bool from_cand = false; // the polish refactored from a candidate that passed its check
+  bool parked = false;    // the ADMM inverse is in the park slab
+  int nfail = 0;          // failed sessions so far (the memory holds the last kFailMem)
+  int ntried = 0;         // face sets tried in the current session
+  bool seen_start = false;  // the current session started from a remembered failed set
+  int last_pol = 0;       // iteration of the last polish session
+  bool fail_rho_done = false;  // rho moved to kFailRho x rho0 after the first failed session
+  bool warm_session = false;  // the current polish session is the warm start's
+};
+
+// The faces a force on the pyramid lies on, to fp32 rounding (polish face code: 1 fz at fz_min,
+// 2 / 4 fx at +/- mu fz, 8 / 16 fy alike).  `slack` is what the friction limit mu fz gives way
+// by; the callers differ in it.
+__device__ __forceinline__ int faces_at(float fx, float fy, float fz, float mu, float fz_min,
+                                        float slack) {
+  const float tz = 1e-5f * fmaxf(fz, 1.f), lim = mu * fz - slack;
+  int code = (fz <= fz_min + tz) ? 1 : 0;
+  code |= (fx >= lim) ? 2 : (fx <= -lim) ? 4 : 0;
+  code |= (fy >= lim) ? 8 : (fy <= -lim) ? 16 : 0;
+  return code;
+}
+
+// Instance staging: global loads, validation and staging of Q / R, the stance triples, d_k, the
+// ADMM basis and the nilpotent test.  Sets I's fields from weights_ok on (b, N, NP, T are the
+// caller's).
+template <int NC>
+__device__ __forceinline__ void stage_instance(Smem<NC>& s, const KParams& P, const Inputs& in,
+                                               Instance& I, int lane) {
+  const int64_t b = I.b;
+  const int N = I.N, NP = I.NP;
+  const Terrain T = I.T;
   // per-instance weights (Inputs::Q / R): valid?  and the strong-convexity modulus min_i R2[i]
   // of this instance; both wave-uniform scalars like T, set with the staging loads below
   bool weights_ok = true;
   float r2_min = P.r2_min;
-#if defined(CMPC_POISON_LDS)  // diagnostic: NaN into the float scratch before every instance
-  if constexpr (W == 1) {
-    const float qn = __int_as_float(0x7fc00000);
-    for (int i = lane; i < 12 * NC; i += 64) s.G[i] = qn;
-    for (int i = lane; i < NC; i += 64) s.v[i] = qn;
-    WSYNC();
-  }
-#endif
-#if defined(CMPC_POISON_PARK)  // diagnostic: NaN into the wave's park slab before every instance
-  if constexpr (W == 1) {
-    const float qn = __int_as_float(0x7fc00000);
-    for (int i = lane; i < Cfg<NC>::SLAB; i += 64) park[i] = qn;
-  }
-#endif
   const float* Ab = in.Ad + b * 144;
   const float* Bg = in.Bd + b * (int64_t)N * 144;
   const float* gdb = in.gd + b * 12;
   const float* x0b = in.x0 + b * 12;
   const float* xrb = in.xref + b * (int64_t)N * 12;
   const uint8_t* ctb = in.contact + b * (int64_t)4 * N;
-  CMPC_T0(t_inst);
-  CMPC_CNT(10, 1);
 
   WSYNC();
   {  // one round of global loads: A, r_0..r_N (= x0, xref), gd; staged in LDS (G is free here)
@@ -2104,29 +2129,30 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
     }
     build_admm_basis<NC>(s, P, Bg, ntri);
   }
-  const int n = 3 * ntri;
   const bool nil = nilpotent_step(s);  // A = I + N, N^2 = 0: the closed-form condensation
   if (lane == 0) s.nil = nil ? 1 : 0;   // (and the gradient's powers of A)
   WSYNC();
-  // team mode: the gradient's powers of A once per instance (registers to spare: the tiles are
-  // split over the team)
-  // (NC <= 128 only: the larger bins need those registers for their tiles)
-  constexpr bool kPow = W > 1 && NC <= 128;
-  f4 pw_c[4], tw_c[4];
-  if constexpr (kPow) gradient_powers(s, pw_c, tw_c);
-  const f4* pwc = kPow ? pw_c : nullptr;
-  const f4* twc = kPow ? tw_c : nullptr;
-  // initial rho per bin: the NC >= 128 bins (33-64 stance triples) converge in fewer iterations
-  // from rho0 / 2; their hard instances (a failed polish session) go back to rho0, where they
-  // converge as before (NC = 128: cfg1 +6-10 %, cfg2 +1 %; NC >= 160: kRhoLowHeavy; rho0 / 2
-  // for the NC = 96 bin too loses 7 % on cfg2)
-  constexpr bool kLow = (NC == 128) || (kRhoLowHeavy && NC > 128);
-  float rho = kLow ? 0.5f * P.rho0 : P.rho0;
-  bool rho_low = kLow;  // still at the bin's reduced initial rho
+  I.weights_ok = weights_ok;
+  I.r2_min = r2_min;
+  I.Bg = Bg;
+  I.xrb = xrb;
+  I.ntri = ntri;
+  I.n = 3 * ntri;
+  I.nil = nil;
+}
+
+// Starting point: x = z = y = 0 (cold), or the warm start from w_init, y_init or lam_init.
+// s.pcode seeds the polish trigger (-1: no face set yet).
+template <int NC>
+__device__ __forceinline__ void starting_point(Smem<NC>& s, const Inputs& in, const Instance& I,
+                                               float rho, int lane) {
+  const int64_t b = I.b;
+  const int N = I.N, NP = I.NP, n = I.n;
+  const Terrain T = I.T;
   s.pcode[lane] = -1;
   if (in.w_init == nullptr && in.y_init == nullptr && in.lam_init == nullptr) {
     for (int p = lane; p < n; p += 64) { s.x[p] = 0.f; s.z[p] = 0.f; s.y[p] = 0.f; }
-  } else if (lane < ntri) {
+  } else if (lane < I.ntri) {
     // warm start (the reference's x0 / lam_x0 of centroidal_mpc.py:91-95): triple `lane`
     // (step k, leg l) starts at x = z = Pi_K(u_init), y = y_init; its face code seeds the
     // polish trigger with the projection of u + y / rho, the first z-update's argument
@@ -2166,11 +2192,8 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
       const float ir = 1.f / rho;
       code = project(pv[0] + yv[0] * ir, pv[1] + yv[1] * ir, pv[2] + yv[2] * ir, T.mu, T.fz_min,
                      qv[0], qv[1], qv[2]);
-    } else {          // primal only: the faces the warm point lies on, to fp32 rounding
-      const float tz = 1e-5f * fmaxf(pv[2], 1.f), lim = T.mu * pv[2] - 1e-5f * pv[2];
-      code = (pv[2] <= T.fz_min + tz) ? 1 : 0;
-      code |= (pv[0] >= lim) ? 2 : (pv[0] <= -lim) ? 4 : 0;
-      code |= (pv[1] >= lim) ? 8 : (pv[1] <= -lim) ? 16 : 0;
+    } else {          // primal only: the faces the warm point lies on
+      code = faces_at(pv[0], pv[1], pv[2], T.mu, T.fz_min, 1e-5f * pv[2]);
     }
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -2180,505 +2203,489 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
     }
     s.pcode[lane] = code;
   }
+}
 
-  CMPC_ACC(6, t_inst);
-  // ADMM state (x, z, y of triple t at 3t .. 3t+2) lives in LDS, not in registers
-
-  int status = -2, iters = 0;
-#ifdef CMPC_DIAG_GRES
-  float dg_gm = -1.f, dg_cm = -1.f, dg_us = 0.f;  // (-1: not a polished point)
-#endif
-#ifdef CMPC_DIAG_COUNTS
-  int dg_fact = 0, dg_pol = 0, dg_flags = 0;
-  unsigned long long dg_t0 = __builtin_amdgcn_s_memtime();
-  float dg_fail_t[4] = {0.f, 0.f, 0.f, 0.f};  // cycles at the end of failed sessions 1..4
-  int dg_fail_f[4] = {0, 0, 0, 0};            // factorizations by then
-  int dg_nf = 0;
-#endif
-#ifdef CMPC_DIAG_TIMES  // diagnostic build: start / end on the 100 MHz constant clock
-  unsigned long long dt_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
-  bool polished = false;
-  float rp = 0.f, rd = 0.f, np_ = 0.f, nd = 0.f;
-  int stable = 0;
-  bool refactor = n > 0;  // (re)build + invert the matrix for the current basis
-  bool in_polish = false;
-  int nact = n;           // params of the current basis
-  float shift = uniformf(P.sigma + rho);
-  int it = 0;
-  int repairs_left = 0;
-  int nadd = 0;           // faces added by downdates since the last factorization
-  bool from_cand = false; // the polish refactored from a candidate that passed its check
-  bool parked = false;    // the ADMM inverse is in the park slab
-  int nfail = 0;          // failed sessions so far (the memory holds the last kFailMem)
-  int ntried = 0;         // face sets tried in the current session
-  bool seen_start = false;  // the current session started from a remembered failed set
-  int last_pol = 0;       // iteration of the last polish session
-  bool fail_rho_done = false;  // rho moved to kFailRho x rho0 after the first failed session
-  const float alpha = P.alpha;
-  if (n == 0) status = 1;
-  bool warm_session = false;  // the current polish session is the warm start's
-  if (n > 0 && in.w_init != nullptr) {
-    // warm active set: the face set of the warm point goes straight to the polish (one
-    // reduced factorization instead of the ADMM one + the polish one); if its KKT check and
-    // repairs fail, the instance restarts as a cold solve (below)
-    warm_session = true;
-    WSYNC();
-    if (lane < ntri) s.code[lane] = s.pcode[lane];
-    repairs_left = session_start<NC>(s, P, ntri, nfail, ntried, seen_start);
-    nact = polish_setup<NC>(s, P, T, Bg, ntri, s.z);
-    shift = P.sigma;
-    in_polish = true;
+// Factorization: the only condense + invert call site.
+template <int NC, int W>
+__device__ __forceinline__ void factorize(Smem<NC>& s, const KParams& P, const Instance& I, Ctl& c,
+                                          f4 (&M)[TeamCfg<NC, W>::SLOTS], TeamSmem<NC, W>* ts,
+                                          int* seq, Diag& diag, int lane) {
+  CMPC_CNT(8, 1);
+  TRACEF(I.b, "it %d FACTOR polish %d nact %d shift %g\n", c.it, (int)c.in_polish, c.nact, c.shift);
+  diag.factor();
+  if constexpr (W == 1) {
+    CMPC_T0(t_c);
+    condense_tiles<NC>(s, P, M, c.nact, uniformf(c.shift), I.nil);
+    CMPC_ACC(0, t_c);
+    CMPC_T0(t_i);
+    ldl_tiles<NC>(s, M, c.nact);
+    CMPC_ACC(1, t_i);
+  } else {
+    CMPC_T0(t_c);
+    team_factor_lead<NC, W>(s, *ts, *seq, P, M, c.nact, uniformf(c.shift));
+    CMPC_ACC(0, t_c);
   }
-  while (n > 0) {
-    if (refactor) {  // the only condense + invert call site
-      CMPC_CNT(8, 1);
-#ifdef CMPC_TRACE
-      if (trace_on(b) && lane == 0)
-        printf("[%d] it %d FACTOR polish %d nact %d shift %g\n", (int)b, it, (int)in_polish, nact, shift);
-#endif
-#ifdef CMPC_DIAG_COUNTS
-      ++dg_fact;
-#endif
+  c.refactor = false;
+}
+
+// A polish session opens on the face set in s.code: its repair budget and memory
+// (session_start), the reduced basis (polish_setup from ADMM's z), and a factorization of it.
+template <int NC>
+__device__ __forceinline__ void enter_polish(Smem<NC>& s, const KParams& P, const Instance& I,
+                                             Ctl& c) {
+  c.repairs_left = session_start<NC>(s, P, I.ntri, c.nfail, c.ntried, c.seen_start);
+  c.nact = polish_setup<NC>(s, P, I.T, I.Bg, I.ntri, s.z);
+  c.nadd = 0;
+  c.shift = P.sigma;
+  c.refactor = true;
+  c.in_polish = true;
+}
+
+// The current face set gets a fresh basis (polish_setup from the forces `from`) and a
+// factorization; the downdates are gone.
+template <int NC>
+__device__ __forceinline__ void refactor_faces(Smem<NC>& s, const KParams& P, const Instance& I,
+                                               Ctl& c, const float* from) {
+  c.nact = polish_setup<NC>(s, P, I.T, I.Bg, I.ntri, from);
+  c.nadd = 0;
+  c.shift = P.sigma;
+  c.refactor = true;
+}
+
+// What polish_refine leaves: the last refinement step, the scale of v, whether the steps
+// stopped contracting, and the KKT check at the final point.
+struct Refined {
+  float step, vscale;
+  bool stalled;
+  PolishCheck chk;
+};
+
+// Iterative refinement v -= M (grad): polish_refine steps, then more (up to kRefineExtra)
+// while the step still contracts and is above the acceptance tolerance -- an ill-conditioned
+// face set (internal foot forces weigh only R) contracts slowly -- and then the KKT check.
+template <int NC, int W>
+__device__ __forceinline__ Refined polish_refine(Smem<NC>& s, const KParams& P, const Instance& I,
+                                                 Ctl& c, f4 (&M)[TeamCfg<NC, W>::SLOTS],
+                                                 TeamSmem<NC, W>* ts, int* seq, int lane) {
+  Refined r;
+  r.step = 3.0e38f;
+  r.vscale = 1.f;
+  r.stalled = false;
+  float prev = 3.0e38f;
+  const int nact = c.nact;
+  // refinement steps before the convergence test may stop them: polish_refine from ADMM's
+  // rough point; one from a candidate that already passed the check (a stall re-check)
+  const int qmin = c.from_cand ? 1 : P.polish_refine;
+  c.from_cand = false;
+  for (int pass = 0;; ++pass) {
+    // (an extra pass -- ambiguous face multipliers, below -- is one more refinement step)
+    for (int q = pass == 0 ? 0 : P.polish_refine + kRefineExtra - 1;
+         q < P.polish_refine + kRefineExtra; ++q) {
+      gradient<NC, (W > 1), true>(s, P, nact, s.v, s.g, I.pwc, I.twc);
       if constexpr (W == 1) {
-        CMPC_T0(t_c);
-        condense_tiles<NC>(s, P, M, nact, uniformf(shift), nil);
-        CMPC_ACC(0, t_c);
-        CMPC_T0(t_i);
-        ldl_tiles<NC>(s, M, nact);
-        CMPC_ACC(1, t_i);
+        minv_apply<NC>(s, P, M, nact, s.g, s.dl);
+        if (c.nadd > 0) dd_apply<NC>(s, nact, c.nadd, s.g, s.dl);  // (uniform)
       } else {
-        CMPC_T0(t_c);
-        team_factor_lead<NC, W>(s, *ts, *seq, P, M, nact, uniformf(shift));
-        CMPC_ACC(0, t_c);
+        team_symv_lead<NC, W>(s, *ts, *seq, M, nact, s.g, s.dl);
       }
-      refactor = false;
+      float m = 0.f, mv = 1.f;
+      for (int p = lane; p < nact; p += 64) {
+        const float vn = s.v[p] - s.dl[p];
+        s.v[p] = vn;
+        m = fmaxf(m, fabsf(s.dl[p]));
+        mv = fmaxf(mv, fabsf(vn));
+      }
+      r.step = wave_max(m);
+      r.vscale = wave_max(mv);
+      TRACEF(I.b, "    refine %d step %g\n", q, r.step);
+      r.stalled = r.step > kRefineRate * prev;
+      if (q + 1 >= qmin && (r.step <= P.polish_tol * wave_max(mv) || r.stalled)) break;
+      prev = r.step;
     }
-    if (in_polish) {
-      CMPC_T0(t_pol);
-      // iterative refinement v -= M (grad): polish_refine steps, then more (up to
-      // kRefineExtra) while the step still contracts and is above the acceptance tolerance --
-      // an ill-conditioned face set (internal foot forces weigh only R) contracts slowly
-      float step = 3.0e38f, prev = 3.0e38f, vscale = 1.f;
-      bool ok = false, changed = false, loose = false, converged = false, stalled = false;
-      bool decisive = true;
-      bool amb_last = false;  // (trace)
-      float vworst = 0.f;
-      // refinement steps before the convergence test may stop them: polish_refine from ADMM's
-      // rough point; one from a candidate that already passed the check (a stall re-check)
-      const int qmin = from_cand ? 1 : P.polish_refine;
-      from_cand = false;
-      for (int pass = 0;; ++pass) {
-        // (an extra pass -- ambiguous face multipliers, below -- is one more refinement step)
-        for (int q = pass == 0 ? 0 : P.polish_refine + kRefineExtra - 1;
-             q < P.polish_refine + kRefineExtra; ++q) {
-          gradient<NC, (W > 1), true>(s, P, nact, s.v, s.g, pwc, twc);
-          if constexpr (W == 1) {
-            minv_apply<NC>(s, P, M, nact, s.g, s.dl);
-            if (nadd > 0) dd_apply<NC>(s, nact, nadd, s.g, s.dl);  // (uniform)
-          } else {
-            team_symv_lead<NC, W>(s, *ts, *seq, M, nact, s.g, s.dl);
-          }
-          float m = 0.f, mv = 1.f;
-          for (int p = lane; p < nact; p += 64) {
-            const float vn = s.v[p] - s.dl[p];
-            s.v[p] = vn;
-            m = fmaxf(m, fabsf(s.dl[p]));
-            mv = fmaxf(mv, fabsf(vn));
-          }
-          step = wave_max(m);
-          vscale = wave_max(mv);
-  #ifdef CMPC_TRACE
-          if (trace_on(b) && lane == 0) printf("[%d]     refine %d step %g\n", (int)b, q, step);
-  #endif
-          stalled = step > kRefineRate * prev;
-          if (q + 1 >= qmin && (step <= P.polish_tol * wave_max(mv) || stalled)) break;
-          prev = step;
-        }
-        gradient<NC, (W > 1), true>(s, P, nact, s.v, s.g, pwc, twc);  // E, L at the final point
-        // a hard instance's later repairs move only the worst triples: full primal-dual
-        // active-set steps swap several faces at a time and can wander between neighbouring sets
-        const int top = (kRepairTop > 0 && (nfail > 0 || ntried >= 3)) ? kRepairTop : 0;
-        bool amb = false;
-  #ifdef CMPC_TRACE
-        ok = polish_check<NC>(s, P, T, Bg, ntri, step, changed, loose, converged, amb, decisive,
-                              vworst, top, trace_on(b) ? (int)b : -1);
-  #else
-        ok = polish_check<NC>(s, P, T, Bg, ntri, step, changed, loose, converged, amb, decisive,
-                              vworst, top);
-  #endif
-        amb_last = amb;
-        // A face multiplier near zero decides the check but moves by ~|H| x the point's remaining
-        // error (a step accepted at polish_tol x the force scale leaves ~1e-5 N, i.e. ~1e-7 in a
-        // multiplier -- the force-unit tolerance's size: config-3 instance 54289 passed with fz
-        // held at fz_min, multiplier -3e-8 at its point, -1.3e-6 at the converged one, a
-        // 1.2e-4 error; next-tick 55062 warm held fy at mu fz with +2.5e-7 at its point,
-        // -3.2e-7 converged, 1.06e-4).  Such a check is repeated after further refinement steps.
-        if (!(amb && (ok || loose)) || pass >= kAmbRefine ||
-            step <= kAmbConverged * P.polish_tol * vscale)
-          break;
-      }
-#ifdef CMPC_TRACE
-      if (trace_on(b) && lane == 0)
-        printf("[%d] it %d polish nact %d nadd %d ok %d loose %d changed %d amb %d dec %d step %g "
-               "stalled %d repairs_left %d ntried %d nfail %d\n", (int)b, it, nact, nadd, (int)ok,
-               (int)loose, (int)changed, (int)amb_last, (int)decisive, step, (int)stalled,
-               repairs_left, ntried, nfail);
-#endif
-      CMPC_ACC(4, t_pol);
-      // A refinement on a downdated inverse that stopped contracting above the tight level
-      // (fp32 downdates of an ill-conditioned face set: steps 1e-4, 3.1e-5, 2.9e-5) leaves
-      // multipliers near zero unreliable -- config-3 instance 31861 held a degenerate friction
-      // face at -1.6e-7, released it, found it violated, and cycled through 5 sessions and 130
-      // ADMM iterations.  When only such multipliers fail the check, the face set is refactored
-      // exactly before the check decides.  (Refactoring every stalled downdate also fixed 31861
-      // but cost 6-10 % more factorizations on configs 2-3: most stalls sit at the fp32 floor
-      // of checks that large violations decide anyway.)
-      // Nor is a point accepted while a downdated refinement stopped contracting above the
-      // fp32 floor: the step is then no bound on the point's error (config-3 instance 39503:
-      // three downdates, steps 2.2e-4, 5.7e-4, 5.0e-4 against a tolerance of 9.7e-4, accepted
-      // 0.037 N = 3.8e-4 off; 25651: one downdate, steps 6.8e-5, 4.3e-5, 1.0e-4, 2.0e-4 off).
-      // The face set is refactored and refined afresh first (round 6: the guard is the product
-      // rule -- 9.5 % of config-3 instances, 18 % of config 2's, pass a check on such a
-      // refinement, so answering them as status 2 instead was no option; profiles/r06a_*)
-      const bool dd_stalled = nadd > 0 && stalled && step > kAmbConverged * P.polish_tol * vscale;
-      const bool dd_stall = dd_stalled && (ok || loose || !decisive);
-      if (dd_stall) {
-        converged = false;
-        if (out.stats != nullptr && lane == 0) atomicAdd(&out.stats[2], 1ull);  // (rare)
-#ifdef CMPC_DIAG_COUNTS
-        dg_flags |= 4;
-#endif
-      }
-      // status 1 contract (include/cmpc.h): the check passed on a refinement that converged
-      // (and, after downdates, still contracted), and the held faces' certified force error is
-      // within kCertFace of the force scale (nilpotent step: the float64 rollout's
-      // multipliers); a point that misses the bound is returned as status 2
-      if (ok && !dd_stall) {
-#ifdef CMPC_DIAG_GRES
-        diag_gres<NC>(s, r2_min, nact, dg_gm, dg_cm, dg_us);
-#endif
-        const bool cert = !uniform(s.nil) || certified_faces<NC>(s, r2_min);
-        if (!cert && out.stats != nullptr && lane == 0) atomicAdd(&out.stats[1], 1ull);
-#ifdef CMPC_DIAG_COUNTS
-        if (!cert) dg_flags |= 2;
-#endif
-        polished = true;
-        status = cert ? 1 : 2;
-        break;
-      }
-      if (nadd > 0 && !converged) {
-        // the downdated inverse stopped contracting: refactor the current face set, from the
-        // candidate forces (not a repair)
-#ifdef CMPC_TRACE
-        if (trace_on(b) && lane == 0) printf("[%d] it %d STALL-REFACTOR dd_stall %d\n", (int)b, it, (int)dd_stall);
-#endif
-        nact = polish_setup<NC>(s, P, T, Bg, ntri, s.dl);
-        nadd = 0;
-        shift = P.sigma;
-        refactor = true;
-        from_cand = ok || loose;  // (the guard: the candidate passed; its error is what is checked)
-        continue;
-      }
-      if (repairs_left > 0 && changed && !tried_before<NC>(s, ntri, ntried)) {
-        // re-polish on the repaired face set
-        --repairs_left;
-        bool dd = false;
-        if constexpr (W == 1) {
-          // only added faces: downdate the inverse in the current basis (no refactorization)
-          const int l = opaque_lane();
-          WSYNC();
-          const int oc = (l < ntri) ? s.code[l] : 0, nc = (l < ntri) ? s.tcnt[l] : 0;
-          const int add = nc & ~oc;
-          const int nf = wave_total4((add & 1) + ((add & 6) != 0) + ((add & 24) != 0));
-#ifdef CMPC_TRACE
-          {
-            const bool drop = __any((nc & oc) != oc), freed = __any(((nc ^ oc) & oc & 1) != 0);
-            if (trace_on(b) && lane == 0)
-              printf("[%d] it %d repair drop %d (fz face freed %d) nf %d nadd %d cap %d\n", (int)b,
-                     it, (int)drop, (int)freed, nf, nadd, dd_max(NC));
-          }
-#endif
-          if (__any((nc & oc) != oc) == 0 && nadd + nf <= dd_max(NC)) {  // (uniform)
-            CMPC_T0(t_dd);
-            dd = face_downdate<NC>(s, P, T, M, nact, ntri, nadd);
-#ifdef CMPC_TRACE
-            if (trace_on(b) && lane == 0)
-              printf("[%d] it %d downdate nf %d -> %d nadd %d\n", (int)b, it, nf, (int)dd, nadd);
-#endif
-            CMPC_ACC(28, t_dd);
-            CMPC_CNT(29, 1);
-            CMPC_CNT(30, nf);
-          }
-        }
-        if (lane < ntri) {
-          s.code[lane] = s.tcnt[lane];
-          if (ntried < kTryMem) s.tpat[ntried][lane] = (uint8_t)s.tcnt[lane];
-        }
-        if (ntried < kTryMem) ++ntried;
-        if (dd) continue;  // refine on the downdated inverse
-        nact = polish_setup<NC>(s, P, T, Bg, ntri, s.z);
-        nadd = 0;
-        shift = P.sigma;
-        refactor = true;
-        continue;
-      }
-      if (loose) {  // the session ends on a set within the loose tolerance: accept it
-#ifdef CMPC_DIAG_GRES
-        diag_gres<NC>(s, r2_min, nact, dg_gm, dg_cm, dg_us);
-#endif
-        const bool certok = certified_faces<NC>(s, r2_min);
-        const int l = opaque_lane();
-        WSYNC();
-        if (l < ntri) {  // (projected onto the pyramid: the loose check admits 5x polish_tol)
-          float px, py, pz;
-          project(s.dl[3 * l], s.dl[3 * l + 1], s.dl[3 * l + 2], T.mu, T.fz_min, px, py, pz);
-          s.x[3 * l] = px;
-          s.x[3 * l + 1] = py;
-          s.x[3 * l + 2] = pz;
-        }
-        polished = true;
-        // KKT-verified within the loose bounds only with the float64 rollout (polish_check) and
-        // the certified face bound; a general A's loose acceptance is reported as not verified
-        status = (uniform(s.nil) && certok) ? 1 : 2;
-        if (out.stats != nullptr && lane == 0) {
-          atomicAdd(&out.stats[0], 1ull);
-          if (!certok) atomicAdd(&out.stats[1], 1ull);
-        }
-#ifdef CMPC_DIAG_COUNTS
-        dg_flags |= 1 | (certok ? 0 : 2);
-#endif
-        break;
-      }
-      if (warm_session) {
-        // The warm face set failed (the state moved across a face change): restart exactly as
-        // the cold solve of this problem -- x = z = y = 0, the bin's initial rho, no failed
-        // session on record -- so a warm start never takes more ADMM iterations than cold.
-        // (Continuing ADMM from the warm (x, z, y) counted the warm set as a failed session:
-        // 4 x rho0, 3x the stable run, the back-off -- the hard-instance schedule -- and the
-        // round-4 bench's warm maximum was 253 iterations against 107 cold.)
-        warm_session = false;
-        build_admm_basis<NC>(s, P, Bg, ntri);  // (zeroes x, z, y past n)
-        {
-          const int l = opaque_lane();
-          for (int p = l; p < n; p += 64) { s.x[p] = 0.f; s.z[p] = 0.f; s.y[p] = 0.f; }
-          s.pcode[l] = -1;
-        }
-        WSYNC();
-        in_polish = false;
-        nact = n;
-        nadd = 0;
-        rho = kLow ? 0.5f * P.rho0 : P.rho0;
-        rho_low = kLow;
-        shift = uniformf(P.sigma + rho);
-        refactor = true;
-        stable = 0;
-        last_pol = 0;
-        ntried = 0;
-        seen_start = false;
-        parked = false;
-        continue;
-      }
-      warm_session = false;
-#ifdef CMPC_TRACE
-      if (trace_on(b) && lane == 0)
-        printf("[%d] it %d SESSION-FAIL nfail %d seen %d parked %d rho_low %d fail_rho_done %d nadd %d\n",
-               (int)b, it, nfail, (int)seen_start, (int)parked, (int)rho_low, (int)fail_rho_done, nadd);
-#endif
-#ifdef CMPC_DIAG_COUNTS
-      if (dg_nf < 4) {
-        dg_fail_t[dg_nf] = (float)(__builtin_amdgcn_s_memtime() - dg_t0);
-        dg_fail_f[dg_nf] = dg_fact;
-      }
-      ++dg_nf;
-#endif
-      // the session failed: remember its starting face set (unless it came from the memory)
-      if (!seen_start) {
-        const int l = opaque_lane();
-        if (l < ntri) s.fpat[nfail % kFailMem][l] = s.tpat[0][l];
-        ++nfail;
-      }
-      // restore the basis and the parked ADMM inverse (or rebuild it first), continue ADMM
-      build_admm_basis<NC>(s, P, Bg, ntri);
-      in_polish = false;
-      nact = n;
-      if (nfail == 1 && !seen_start && kFailRho != 1.f && !fail_rho_done) {
-        // the first failed session: a hard instance continues at kFailRho x rho0 (one refactor;
-        // nothing is parked before the second session, so it would refactor anyway)
-        fail_rho_done = true;
-        rho_low = false;
-        rho = uniformf(kFailRho * P.rho0);
-        shift = uniformf(P.sigma + rho);
-        refactor = true;
-        continue;
-      }
-      if (rho_low) {  // a hard instance: back to the standard rho0 (one refactor)
-        rho_low = false;
-        rho = uniformf(P.rho0);
-        shift = uniformf(P.sigma + rho);
-        refactor = true;
-        continue;
-      }
-      shift = uniformf(P.sigma + rho);
-      if (parked) {
-        if constexpr (W == 1) {
-          park_load<NC>(park, M);
-        } else {
-          team_issue<NC, W>(*ts, *seq, kOpParkLoad, 0, 0, 0);
-          team_park_load<NC, W, 0>(park, M, 0);
-        }
-      } else {
-        refactor = true;  // M holds the polish inverse: refactor before the next iteration
-        continue;
-      }
-    }
-    if (it >= P.max_iter) break;
-    ++it;
-    iters = it;
-    // ---- one ADMM iteration ----
-    gradient<NC, (W > 1)>(s, P, n, s.x, s.g, pwc, twc);
-    {
-      const int l = opaque_lane();
-      if (l < ntri) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          const int p = 3 * l + a;
-          s.r[p] = rho * (s.z[p] - s.x[p]) - s.g[p] - s.y[p];
-        }
-      }
-    }
-    if constexpr (W == 1) {
-      minv_apply<NC>(s, P, M, n, s.r, s.dl);
-    } else {
-      team_symv_lead<NC, W>(s, *ts, *seq, M, n, s.r, s.dl);
-    }
-    CMPC_T0(t_rest);
-    const bool last = (it == P.max_iter);
-    const bool adapt = P.adaptive_interval > 0 && (it % P.adaptive_interval) == 0;
-    const float inv_rho = 1.f / rho;
-    float lrp = 0.f, lrd = 0.f, lnp = 0.f, lnd = 0.f;
-    bool changed = false;
-    {
-      const int l = opaque_lane();
-      if (l < ntri) {
-        float w[3], xr[3], xs[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          const int p = 3 * l + a;
-          const float x = s.x[p], z = s.z[p];
-          const float xt = x + s.dl[p];
-          xr[a] = alpha * xt + (1.f - alpha) * z;
-          xs[a] = alpha * xt + (1.f - alpha) * x;
-          w[a] = xr[a] + s.y[p] * inv_rho;
-        }
-        float pv[3];
-        const int code = project(w[0], w[1], w[2], T.mu, T.fz_min, pv[0], pv[1], pv[2]);
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          const int p = 3 * l + a;
-          const float zn = pv[a];
-          const float yn = s.y[p] + rho * (xr[a] - zn);
-          s.x[p] = xs[a];
-          s.z[p] = zn;
-          s.y[p] = yn;
-          const float gp = s.g[p];
-          lrp = fmaxf(lrp, fabsf(xs[a] - zn));
-          lrd = fmaxf(lrd, fabsf(gp + yn));
-          lnp = fmaxf(lnp, fmaxf(fabsf(xs[a]), fabsf(zn)));
-          lnd = fmaxf(lnd, fmaxf(fabsf(gp), fabsf(yn)));
-        }
-        changed = code != s.pcode[l];
-        s.pcode[l] = code;
-        s.code[l] = code;
-      }
-    }
-#ifdef CMPC_TRACE
-    if (trace_on(b)) {
-      const float trp = wave_max(lrp), trd = wave_max(lrd);
-      if (lane == 0)
-        printf("[%d] it %d rho %g rp %g rd %g stable %d\n", (int)b, it, rho, trp, trd, stable);
-    }
-#endif
-    stable = (__any(changed) != 0) ? 0 : stable + 1;
-    bool do_pol = false;
-    // back off before a further attempt, longer after failed sessions: both the stable run and
-    // the distance to the last session grow as polish_stable x 2^min(nfail, kBackoffCap)
-    const int pstable = P.polish_stable;
-    const int backoff = pstable << min(nfail, kBackoffCap);
-    int need = pstable;  // (kStableGrow: the stable run required grows per failed session)
-    for (int f = 0; f < min(nfail, kBackoffCap); ++f) need *= kStableGrow;
-    if (stable >= need && !last && it - last_pol >= backoff &&
-        (P.check_every == 1 || it % P.check_every == 0)) {  // (OPTS check_termination)
-      do_pol = true;
-      last_pol = it;
-      stable = -backoff;
-    }
-    if (adapt || last) {
-      rp = wave_max(lrp); rd = wave_max(lrd); np_ = wave_max(lnp); nd = wave_max(lnd);
-    }
-    if (adapt && !last) {
-      float q = rho * sqrtf((rp / fmaxf(np_, 1e-30f)) / (rd / fmaxf(nd, 1e-30f) + 1e-30f));
-      q = fminf(fmaxf(q, 1e-6f), 1e6f);
-      if (q > 5.f * rho || q < 0.2f * rho) {
-        rho = uniformf(q);
-        rho_low = false;
-        shift = uniformf(P.sigma + rho);
-        refactor = true;
-      }
-    }
-    CMPC_ACC(7, t_rest);
-    if (do_pol) {
-      CMPC_CNT(9, 1);
-#ifdef CMPC_DIAG_COUNTS
-      ++dg_pol;
-#endif
-      CMPC_T0(t_ps);
-      // Park (write the 36-108 KB inverse to the wave's slab) only where a failed session will
-      // restore it: not when a refactor is pending (rho changed: the inverse is stale), not at
-      // the NC = 128 bin's reduced rho (a failure refactors at rho0), and not in the first
-      // session (most instances pass it; the few that fail refactor once).  HBM writes of a
-      // config-3 step drop from ~36 KB to a few hundred bytes per instance at unchanged speed.
-      parked = !refactor && !rho_low && nfail > 0;
-      if (parked) {  // restored if the polish fails
-        if constexpr (W == 1) {
-          park_store<NC>(park, M);
-        } else {
-          team_issue<NC, W>(*ts, *seq, kOpParkStore, 0, 0, 0);
-          team_park_store<NC, W, 0>(park, M, 0);
-        }
-      }
-      repairs_left = session_start<NC>(s, P, ntri, nfail, ntried, seen_start);
-      nact = polish_setup<NC>(s, P, T, Bg, ntri, s.z);
-      nadd = 0;
-#ifdef CMPC_TRACE
-      if (trace_on(b) && lane == 0)
-        printf("[%d] it %d SESSION nfail %d parked %d rho %g refactor_pending %d seen %d repairs %d nact %d\n",
-               (int)b, it, nfail, (int)parked, rho, (int)refactor, (int)seen_start, repairs_left, nact);
-#endif
-      CMPC_ACC(14, t_ps);
-      shift = P.sigma;
-      refactor = true;
-      in_polish = true;
-    }
+    gradient<NC, (W > 1), true>(s, P, nact, s.v, s.g, I.pwc, I.twc);  // E, L at the final point
+    // a hard instance's later repairs move only the worst triples: full primal-dual
+    // active-set steps swap several faces at a time and can wander between neighbouring sets
+    const int top = (kRepairTop > 0 && (c.nfail > 0 || c.ntried >= 3)) ? kRepairTop : 0;
+    r.chk = polish_check<NC>(s, P, I.T, I.Bg, I.ntri, r.step, top, trace_id(I.b));
+    // A face multiplier near zero decides the check but moves by ~|H| x the point's remaining
+    // error (a step accepted at polish_tol x the force scale leaves ~1e-5 N, i.e. ~1e-7 in a
+    // multiplier -- the force-unit tolerance's size: config-3 instance 54289 passed with fz
+    // held at fz_min, multiplier -3e-8 at its point, -1.3e-6 at the converged one, a
+    // 1.2e-4 error; next-tick 55062 warm held fy at mu fz with +2.5e-7 at its point,
+    // -3.2e-7 converged, 1.06e-4).  Such a check is repeated after further refinement steps.
+    if (!(r.chk.amb && (r.chk.ok || r.chk.loose)) || pass >= kAmbRefine ||
+        r.step <= kAmbConverged * P.polish_tol * r.vscale)
+      break;
   }
-  if (!polished) {
-    if (n > 0) {
-      const bool conv = rp <= P.eps_abs + P.eps_rel * np_ && rd <= P.eps_abs + P.eps_rel * nd;
-      status = conv ? 2 : -2;
-    }
-    gradient<NC, (W > 1)>(s, P, n, s.z, s.g, pwc, twc);  // E at u = z (the pure rollout when every leg swings)
+  return r;
+}
+
+// What one polish pass decided; solve_instance's switch makes the state changes.
+enum class Polish {
+  kAccepted,         // the check passed: the forces are in s.x
+  kAcceptedLoose,    // the session ends on a set within the loose tolerance (candidate in s.dl)
+  kRefactorSameSet,  // a downdated refinement stalled: same faces, fresh factorization
+  kRepaired,         // the check proposes a face set (s.tcnt) this session has not tried
+  kWarmRestart,      // the warm start's session failed: restart as the cold solve
+  kSessionFailed     // back to ADMM
+};
+
+// One polish pass: refinement, check, and exactly one decision.
+template <int NC, int W>
+__device__ __forceinline__ Polish polish_pass(Smem<NC>& s, const KParams& P, const Instance& I,
+                                              const Outputs& out, Ctl& c,
+                                              f4 (&M)[TeamCfg<NC, W>::SLOTS], TeamSmem<NC, W>* ts,
+                                              int* seq, Diag& diag, int lane) {
+  CMPC_T0(t_pol);
+  Refined r = polish_refine<NC, W>(s, P, I, c, M, ts, seq, lane);
+  const bool ok = r.chk.ok, loose = r.chk.loose;
+  TRACEF(I.b, "it %d polish nact %d nadd %d ok %d loose %d changed %d amb %d dec %d step %g "
+         "stalled %d repairs_left %d ntried %d nfail %d\n", c.it, c.nact, c.nadd, (int)ok,
+         (int)loose, (int)r.chk.changed, (int)r.chk.amb, (int)r.chk.decisive, r.step,
+         (int)r.stalled, c.repairs_left, c.ntried, c.nfail);
+  CMPC_ACC(4, t_pol);
+  // A refinement on a downdated inverse that stopped contracting above the tight level
+  // (fp32 downdates of an ill-conditioned face set: steps 1e-4, 3.1e-5, 2.9e-5) leaves
+  // multipliers near zero unreliable -- config-3 instance 31861 held a degenerate friction
+  // face at -1.6e-7, released it, found it violated, and cycled through 5 sessions and 130
+  // ADMM iterations.  When only such multipliers fail the check, the face set is refactored
+  // exactly before the check decides.  (Refactoring every stalled downdate also fixed 31861
+  // but cost 6-10 % more factorizations on configs 2-3: most stalls sit at the fp32 floor
+  // of checks that large violations decide anyway.)
+  // Nor is a point accepted while a downdated refinement stopped contracting above the
+  // fp32 floor: the step is then no bound on the point's error (config-3 instance 39503:
+  // three downdates, steps 2.2e-4, 5.7e-4, 5.0e-4 against a tolerance of 9.7e-4, accepted
+  // 0.037 N = 3.8e-4 off; 25651: one downdate, steps 6.8e-5, 4.3e-5, 1.0e-4, 2.0e-4 off).
+  // The face set is refactored and refined afresh first (round 6: the guard is the product
+  // rule -- 9.5 % of config-3 instances, 18 % of config 2's, pass a check on such a
+  // refinement, so answering them as status 2 instead was no option; profiles/r06a_*)
+  const bool dd_stalled =
+      c.nadd > 0 && r.stalled && r.step > kAmbConverged * P.polish_tol * r.vscale;
+  const bool dd_stall = dd_stalled && (ok || loose || !r.chk.decisive);
+  if (dd_stall) {
+    r.chk.converged = false;
+    if (out.stats != nullptr && lane == 0) atomicAdd(&out.stats[2], 1ull);  // (rare)
+    diag.flag(Diag::kDdStall);
   }
-#ifdef CMPC_TRACE
-  if (trace_on(b) && lane == 0) printf("[%d] END status %d iters %d\n", (int)b, status, iters);
-#endif
-  CMPC_T0(t_out);
-  // ---- outputs: x_{k+1} = e_{k+1} + xref_k, u from the triples (zero on swing legs) ----
+  if (ok && !dd_stall) return Polish::kAccepted;
+  if (c.nadd > 0 && !r.chk.converged) {
+    // the downdated inverse stopped contracting: refactor the current face set, from the
+    // candidate forces (not a repair)
+    TRACEF(I.b, "it %d STALL-REFACTOR dd_stall %d\n", c.it, (int)dd_stall);
+    c.from_cand = ok || loose;  // (the guard: the candidate passed; its error is what is checked)
+    return Polish::kRefactorSameSet;
+  }
+  if (c.repairs_left > 0 && r.chk.changed && !tried_before<NC>(s, I.ntri, c.ntried))
+    return Polish::kRepaired;
+  if (loose) return Polish::kAcceptedLoose;
+  return c.warm_session ? Polish::kWarmRestart : Polish::kSessionFailed;
+}
+
+// kAccepted.  Status 1 contract (include/cmpc.h): the check passed on a refinement that
+// converged (and, after downdates, still contracted), and the held faces' certified force error
+// is within kCertFace of the force scale (nilpotent step: the float64 rollout's multipliers); a
+// point that misses the bound is returned as status 2
+template <int NC>
+__device__ __forceinline__ void accept_point(Smem<NC>& s, const Instance& I, const Outputs& out,
+                                             Ctl& c, Diag& diag, int lane) {
+  diag.accepted(s, I.r2_min, c.nact);
+  const bool cert = !uniform(s.nil) || certified_faces<NC>(s, I.r2_min);
+  if (!cert && out.stats != nullptr && lane == 0) atomicAdd(&out.stats[1], 1ull);
+  if (!cert) diag.flag(Diag::kCertMiss);
+  c.polished = true;
+  c.status = cert ? 1 : 2;
+}
+
+// kAcceptedLoose: the candidate forces (s.dl) are the answer.
+template <int NC>
+__device__ __forceinline__ void accept_loose(Smem<NC>& s, const Instance& I, const Outputs& out,
+                                             Ctl& c, Diag& diag, int lane) {
+  diag.accepted(s, I.r2_min, c.nact);
+  const bool certok = certified_faces<NC>(s, I.r2_min);
+  const int l = opaque_lane();
   WSYNC();
-  float* wb = out.w + b * (int64_t)(24 * N);
+  if (l < I.ntri) {  // (projected onto the pyramid: the loose check admits 5x polish_tol)
+    float px, py, pz;
+    project(s.dl[3 * l], s.dl[3 * l + 1], s.dl[3 * l + 2], I.T.mu, I.T.fz_min, px, py, pz);
+    s.x[3 * l] = px;
+    s.x[3 * l + 1] = py;
+    s.x[3 * l + 2] = pz;
+  }
+  c.polished = true;
+  // KKT-verified within the loose bounds only with the float64 rollout (polish_check) and
+  // the certified face bound; a general A's loose acceptance is reported as not verified
+  c.status = (uniform(s.nil) && certok) ? 1 : 2;
+  if (out.stats != nullptr && lane == 0) {
+    atomicAdd(&out.stats[0], 1ull);
+    if (!certok) atomicAdd(&out.stats[1], 1ull);
+  }
+  diag.flag(Diag::kLoose | (certok ? 0 : Diag::kCertMiss));
+}
+
+// kRepaired: re-polish on the repaired face set (s.tcnt), on a downdated inverse where the
+// repair only adds faces, else on a fresh factorization.
+template <int NC, int W>
+__device__ __forceinline__ void repair_faces(Smem<NC>& s, const KParams& P, const Instance& I,
+                                             Ctl& c, f4 (&M)[TeamCfg<NC, W>::SLOTS], int lane) {
+  const int ntri = I.ntri;
+  --c.repairs_left;
+  bool dd = false;
+  if constexpr (W == 1) {
+    // only added faces: downdate the inverse in the current basis (no refactorization)
+    const int l = opaque_lane();
+    WSYNC();
+    const int oc = (l < ntri) ? s.code[l] : 0, nc = (l < ntri) ? s.tcnt[l] : 0;
+    const int add = nc & ~oc;
+    const int nf = wave_total4((add & 1) + ((add & 6) != 0) + ((add & 24) != 0));
+    if (trace_on(I.b)) {
+      const bool drop = __any((nc & oc) != oc), freed = __any(((nc ^ oc) & oc & 1) != 0);
+      TRACEF(I.b, "it %d repair drop %d (fz face freed %d) nf %d nadd %d cap %d\n", c.it,
+             (int)drop, (int)freed, nf, c.nadd, dd_max(NC));
+    }
+    if (__any((nc & oc) != oc) == 0 && c.nadd + nf <= dd_max(NC)) {  // (uniform)
+      CMPC_T0(t_dd);
+      dd = face_downdate<NC>(s, P, I.T, M, c.nact, ntri, c.nadd);
+      TRACEF(I.b, "it %d downdate nf %d -> %d nadd %d\n", c.it, nf, (int)dd, c.nadd);
+      CMPC_ACC(28, t_dd);
+      CMPC_CNT(29, 1);
+      CMPC_CNT(30, nf);
+    }
+  }
+  if (lane < ntri) {
+    s.code[lane] = s.tcnt[lane];
+    if (c.ntried < kTryMem) s.tpat[c.ntried][lane] = (uint8_t)s.tcnt[lane];
+  }
+  if (c.ntried < kTryMem) ++c.ntried;
+  if (dd) return;  // refine on the downdated inverse
+  refactor_faces<NC>(s, P, I, c, s.z);
+}
+
+// kWarmRestart.  The warm face set failed (the state moved across a face change): restart
+// exactly as the cold solve of this problem -- x = z = y = 0, the bin's initial rho, no failed
+// session on record -- so a warm start never takes more ADMM iterations than cold.
+// (Continuing ADMM from the warm (x, z, y) counted the warm set as a failed session:
+// 4 x rho0, 3x the stable run, the back-off -- the hard-instance schedule -- and the
+// round-4 bench's warm maximum was 253 iterations against 107 cold.)
+template <int NC>
+__device__ __forceinline__ void warm_restart(Smem<NC>& s, const KParams& P, const Instance& I,
+                                             Ctl& c) {
+  c.warm_session = false;
+  build_admm_basis<NC>(s, P, I.Bg, I.ntri);  // (zeroes x, z, y past n)
+  {
+    const int l = opaque_lane();
+    for (int p = l; p < I.n; p += 64) { s.x[p] = 0.f; s.z[p] = 0.f; s.y[p] = 0.f; }
+    s.pcode[l] = -1;
+  }
+  WSYNC();
+  c.in_polish = false;
+  c.nact = I.n;
+  c.nadd = 0;
+  c.rho = kRhoLow<NC> ? 0.5f * P.rho0 : P.rho0;
+  c.rho_low = kRhoLow<NC>;
+  c.shift = uniformf(P.sigma + c.rho);
+  c.refactor = true;
+  c.stable = 0;
+  c.last_pol = 0;
+  c.ntried = 0;
+  c.seen_start = false;
+  c.parked = false;
+}
+
+// kSessionFailed: remember the session's starting face set, restore the ADMM basis and go on
+// with ADMM -- at another rho (c.refactor), on the parked inverse, or after a refactor.
+template <int NC, int W>
+__device__ __forceinline__ void session_failed(Smem<NC>& s, const KParams& P, const Instance& I,
+                                               Ctl& c, f4 (&M)[TeamCfg<NC, W>::SLOTS],
+                                               float* __restrict__ park, TeamSmem<NC, W>* ts,
+                                               int* seq, Diag& diag, int lane) {
+  c.warm_session = false;
+  TRACEF(I.b, "it %d SESSION-FAIL nfail %d seen %d parked %d rho_low %d fail_rho_done %d nadd %d\n",
+         c.it, c.nfail, (int)c.seen_start, (int)c.parked, (int)c.rho_low, (int)c.fail_rho_done,
+         c.nadd);
+  diag.session_failed();
+  // the session failed: remember its starting face set (unless it came from the memory)
+  if (!c.seen_start) {
+    const int l = opaque_lane();
+    if (l < I.ntri) s.fpat[c.nfail % kFailMem][l] = s.tpat[0][l];
+    ++c.nfail;
+  }
+  // restore the basis and the parked ADMM inverse (or rebuild it first), continue ADMM
+  build_admm_basis<NC>(s, P, I.Bg, I.ntri);
+  c.in_polish = false;
+  c.nact = I.n;
+  if (c.nfail == 1 && !c.seen_start && kFailRho != 1.f && !c.fail_rho_done) {
+    // the first failed session: a hard instance continues at kFailRho x rho0 (one refactor;
+    // nothing is parked before the second session, so it would refactor anyway)
+    c.fail_rho_done = true;
+    c.rho_low = false;
+    c.rho = uniformf(kFailRho * P.rho0);
+    c.shift = uniformf(P.sigma + c.rho);
+    c.refactor = true;
+    return;
+  }
+  if (c.rho_low) {  // a hard instance: back to the standard rho0 (one refactor)
+    c.rho_low = false;
+    c.rho = uniformf(P.rho0);
+    c.shift = uniformf(P.sigma + c.rho);
+    c.refactor = true;
+    return;
+  }
+  c.shift = uniformf(P.sigma + c.rho);
+  if (c.parked) {
+    if constexpr (W == 1) {
+      park_load<NC>(park, M);
+    } else {
+      team_issue<NC, W>(*ts, *seq, kOpParkLoad, 0, 0, 0);
+      team_park_load<NC, W, 0>(park, M, 0);
+    }
+  } else {
+    c.refactor = true;  // M holds the polish inverse: refactor before the next iteration
+  }
+}
+
+// One ADMM iteration, with the polish trigger and the rho adaptation.  Returns whether a polish
+// session starts now.
+template <int NC, int W>
+__device__ __forceinline__ bool admm_iteration(Smem<NC>& s, const KParams& P, const Instance& I,
+                                               Ctl& c, const f4 (&M)[TeamCfg<NC, W>::SLOTS],
+                                               TeamSmem<NC, W>* ts, int* seq, int lane) {
+  const int n = I.n, ntri = I.ntri, it = c.it;
+  const Terrain T = I.T;
+  const float alpha = P.alpha;
+  float rho = c.rho;
+  gradient<NC, (W > 1)>(s, P, n, s.x, s.g, I.pwc, I.twc);
+  {
+    const int l = opaque_lane();
+    if (l < ntri) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        const int p = 3 * l + a;
+        s.r[p] = rho * (s.z[p] - s.x[p]) - s.g[p] - s.y[p];
+      }
+    }
+  }
+  if constexpr (W == 1) {
+    minv_apply<NC>(s, P, M, n, s.r, s.dl);
+  } else {
+    team_symv_lead<NC, W>(s, *ts, *seq, M, n, s.r, s.dl);
+  }
+  CMPC_T0(t_rest);
+  const bool last = (it == P.max_iter);
+  const bool adapt = P.adaptive_interval > 0 && (it % P.adaptive_interval) == 0;
+  const float inv_rho = 1.f / rho;
+  float lrp = 0.f, lrd = 0.f, lnp = 0.f, lnd = 0.f;
+  bool changed = false;
+  {
+    const int l = opaque_lane();
+    if (l < ntri) {
+      float w[3], xr[3], xs[3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        const int p = 3 * l + a;
+        const float x = s.x[p], z = s.z[p];
+        const float xt = x + s.dl[p];
+        xr[a] = alpha * xt + (1.f - alpha) * z;
+        xs[a] = alpha * xt + (1.f - alpha) * x;
+        w[a] = xr[a] + s.y[p] * inv_rho;
+      }
+      float pv[3];
+      const int code = project(w[0], w[1], w[2], T.mu, T.fz_min, pv[0], pv[1], pv[2]);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        const int p = 3 * l + a;
+        const float zn = pv[a];
+        const float yn = s.y[p] + rho * (xr[a] - zn);
+        s.x[p] = xs[a];
+        s.z[p] = zn;
+        s.y[p] = yn;
+        const float gp = s.g[p];
+        lrp = fmaxf(lrp, fabsf(xs[a] - zn));
+        lrd = fmaxf(lrd, fabsf(gp + yn));
+        lnp = fmaxf(lnp, fmaxf(fabsf(xs[a]), fabsf(zn)));
+        lnd = fmaxf(lnd, fmaxf(fabsf(gp), fabsf(yn)));
+      }
+      changed = code != s.pcode[l];
+      s.pcode[l] = code;
+      s.code[l] = code;
+    }
+  }
+  if (trace_on(I.b)) {
+    const float trp = wave_max(lrp), trd = wave_max(lrd);
+    TRACEF(I.b, "it %d rho %g rp %g rd %g stable %d\n", it, rho, trp, trd, c.stable);
+  }
+  c.stable = (__any(changed) != 0) ? 0 : c.stable + 1;
+  bool do_pol = false;
+  // back off before a further attempt, longer after failed sessions: both the stable run and
+  // the distance to the last session grow as polish_stable x 2^min(nfail, kBackoffCap)
+  const int pstable = P.polish_stable;
+  const int backoff = pstable << min(c.nfail, kBackoffCap);
+  int need = pstable;  // (kStableGrow: the stable run required grows per failed session)
+  for (int f = 0; f < min(c.nfail, kBackoffCap); ++f) need *= kStableGrow;
+  if (c.stable >= need && !last && it - c.last_pol >= backoff &&
+      (P.check_every == 1 || it % P.check_every == 0)) {  // (OPTS check_termination)
+    do_pol = true;
+    c.last_pol = it;
+    c.stable = -backoff;
+  }
+  if (adapt || last) {
+    c.rp = wave_max(lrp); c.rd = wave_max(lrd); c.np_ = wave_max(lnp); c.nd = wave_max(lnd);
+  }
+  if (adapt && !last) {
+    float q = rho * sqrtf((c.rp / fmaxf(c.np_, 1e-30f)) / (c.rd / fmaxf(c.nd, 1e-30f) + 1e-30f));
+    q = fminf(fmaxf(q, 1e-6f), 1e6f);
+    if (q > 5.f * rho || q < 0.2f * rho) {
+      c.rho = uniformf(q);
+      c.rho_low = false;
+      c.shift = uniformf(P.sigma + c.rho);
+      c.refactor = true;
+    }
+  }
+  CMPC_ACC(7, t_rest);
+  return do_pol;
+}
+
+// Session start: parks the ADMM inverse when a failed session will need it back, then opens the
+// session on ADMM's face set.
+template <int NC, int W>
+__device__ __forceinline__ void start_session(Smem<NC>& s, const KParams& P, const Instance& I,
+                                              Ctl& c, const f4 (&M)[TeamCfg<NC, W>::SLOTS],
+                                              float* __restrict__ park, TeamSmem<NC, W>* ts,
+                                              int* seq, Diag& diag, int lane) {
+  CMPC_CNT(9, 1);
+  diag.polish_attempt();
+  CMPC_T0(t_ps);
+  // Park (write the 36-108 KB inverse to the wave's slab) only where a failed session will
+  // restore it: not when a refactor is pending (rho changed: the inverse is stale), not at
+  // the NC = 128 bin's reduced rho (a failure refactors at rho0), and not in the first
+  // session (most instances pass it; the few that fail refactor once).  HBM writes of a
+  // config-3 step drop from ~36 KB to a few hundred bytes per instance at unchanged speed.
+  const bool pending = c.refactor;  // (trace)
+  c.parked = !c.refactor && !c.rho_low && c.nfail > 0;
+  if (c.parked) {  // restored if the polish fails
+    if constexpr (W == 1) {
+      park_store<NC>(park, M);
+    } else {
+      team_issue<NC, W>(*ts, *seq, kOpParkStore, 0, 0, 0);
+      team_park_store<NC, W, 0>(park, M, 0);
+    }
+  }
+  enter_polish<NC>(s, P, I, c);
+  TRACEF(I.b, "it %d SESSION nfail %d parked %d rho %g refactor_pending %d seen %d repairs %d nact %d\n",
+         c.it, c.nfail, (int)c.parked, c.rho, (int)pending, (int)c.seen_start, c.repairs_left,
+         c.nact);
+  CMPC_ACC(14, t_ps);
+}
+
+// Output w: x_{k+1} = e_{k+1} + xref_k, u from the triples (zero on swing legs).  Returns
+// whether every value written is finite.
+template <int NC>
+__device__ __forceinline__ bool write_w(Smem<NC>& s, const Instance& I, float* wb, bool polished,
+                                        int lane) {
+  const int NP = I.NP;
   const float* uf = polished ? s.x : s.z;  // polished forces overwrote x; else u = z
   int bad = 0;
   for (int o = lane; o < NP; o += 64) {
-    const float xv = s.E[o] + xrb[o];
+    const float xv = s.E[o] + I.xrb[o];
     const int k = o / 12, l = (o % 12) / 3, a = o % 3;
     const int t = s.tri_of[4 * k + l];
     const float uv = (t >= 0) ? uf[3 * t + a] : 0.f;
@@ -2686,98 +2693,173 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
     wb[o] = xv;
     wb[NP + o] = uv;
   }
-  if (__any(bad) || !terrain_valid(T) || !weights_ok) status = -10;
-#ifdef CMPC_DIAG_COUNTS  // diagnostic build: w[0..7] = cycles and factorizations at failed sessions 1..4
-  if (lane < 4) wb[lane] = dg_fail_t[lane];
-  else if (lane < 8) wb[lane] = (float)dg_fail_f[lane - 4];
-#endif
-#ifdef CMPC_DIAG_GRES  // diagnostic build: w[0..2] = the gradient and face metrics, the force scale
-  if (lane == 0) { wb[0] = dg_gm; wb[1] = dg_cm; wb[2] = dg_us; }
-#endif
-  if (out.y) {  // dual at the returned forces, in the force layout (zero on swing legs)
-    if (polished && n > 0) {  // y = -grad f(u*) (the ADMM fixed point); s.g is the reduced one
-      build_admm_basis<NC>(s, P, Bg, ntri);
-      gradient<NC, (W > 1)>(s, P, n, s.x, s.g, pwc, twc);
-    }
-    const float* yf = polished ? s.g : s.y;
-    const float sg = polished ? -1.f : 1.f;
-    float* yb = out.y + b * (int64_t)NP;
-    for (int o = lane; o < NP; o += 64) {
-      const int k = o / 12, l = (o % 12) / 3, a = o % 3;
-      const int t = s.tri_of[4 * k + l];
-      yb[o] = (t >= 0) ? sg * yf[3 * t + a] : 0.f;
-    }
+  return __any(bad) == 0;
+}
+
+// Output y: the dual at the returned forces, in the force layout (zero on swing legs).
+template <int NC, int W>
+__device__ __forceinline__ void write_y(Smem<NC>& s, const KParams& P, const Instance& I,
+                                        float* yb, bool polished, int lane) {
+  const int NP = I.NP;
+  if (polished && I.n > 0) {  // y = -grad f(u*) (the ADMM fixed point); s.g is the reduced one
+    build_admm_basis<NC>(s, P, I.Bg, I.ntri);
+    gradient<NC, (W > 1)>(s, P, I.n, s.x, s.g, I.pwc, I.twc);
   }
-  if (out.lam && !weights_ok) {  // an invalid Q / R row has no multipliers: a zero row
-    float* lb = out.lam + b * (int64_t)(52 * N);
+  const float* yf = polished ? s.g : s.y;
+  const float sg = polished ? -1.f : 1.f;
+  for (int o = lane; o < NP; o += 64) {
+    const int k = o / 12, l = (o % 12) / 3, a = o % 3;
+    const int t = s.tri_of[4 * k + l];
+    yb[o] = (t >= 0) ? sg * yf[3 * t + a] : 0.f;
+  }
+}
+
+// Output lam: the reference's multipliers at the returned point (CasADi convention).
+template <int NC>
+__device__ __forceinline__ void write_lam(Smem<NC>& s, const Instance& I, float* lb, bool polished,
+                                          int lane) {
+  const int N = I.N, NP = I.NP;
+  const Terrain T = I.T;
+  if (!I.weights_ok) {  // an invalid Q / R row has no multipliers: a zero row
     for (int o = lane; o < 52 * N; o += 64) lb[o] = 0.f;
-  } else if (out.lam) {  // the reference's multipliers at the returned point (CasADi convention)
-    // L holds lambda_k = the adjoint at the returned forces (the last gradient call), and
-    // lam_eq[k] = -lambda_k (stationarity of x_{k+1}).  Lane 4k + leg: s = 2R u + Bd_k' lambda_k
-    // on its three forces, then the friction-row / bound multipliers of its faces.
+    return;
+  }
+  // L holds lambda_k = the adjoint at the returned forces (the last gradient call), and
+  // lam_eq[k] = -lambda_k (stationarity of x_{k+1}).  Lane 4k + leg: s = 2R u + Bd_k' lambda_k
+  // on its three forces, then the friction-row / bound multipliers of its faces.
+  const float* uf = polished ? s.x : s.z;
+  WSYNC();
+  for (int o = lane; o < NP; o += 64) {
+    lb[o] = 0.f;                 // lam_x of the states (free)
+    lb[24 * N + o] = -s.L[o];    // lam_a of the dynamics rows
+  }
+  if (lane < 4 * N) {
+    const int k = lane >> 2, leg = lane & 3;
+    const int t = s.tri_of[lane];
+    const float* Bk = I.Bg + k * 144 + 3 * leg;
+    float sv[3], u[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      u[a] = (t >= 0) ? uf[3 * t + a] : 0.f;
+      float acc = s.R2[3 * leg + a] * u[a];
+#pragma unroll
+      for (int r = 0; r < 12; ++r) acc = fmaf(Bk[r * 12 + a], s.L[12 * k + r], acc);
+      sv[a] = acc;
+    }
+    float lf[4] = {0.f, 0.f, 0.f, 0.f}, lxv[3] = {0.f, 0.f, 0.f};
+    if (t < 0) {  // swing: f = 0 by equal bounds, lam_x = -s
+#pragma unroll
+      for (int a = 0; a < 3; ++a) lxv[a] = -sv[a];
+    } else {
+      // (not polished: the faces the forces lie on)
+      const int code = polished ? s.code[t]
+                                : faces_at(u[0], u[1], u[2], T.mu, T.fz_min, 1e-5f * fmaxf(u[2], 1.f));
+      // rows: fx - mu fz, -fx - mu fz, fy - mu fz, -fy - mu fz  (centroidal_mpc.py:332-355)
+      if (code & 2) lf[0] = fmaxf(-sv[0], 0.f);
+      if (code & 4) lf[1] = fmaxf(sv[0], 0.f);
+      if (code & 8) lf[2] = fmaxf(-sv[1], 0.f);
+      if (code & 16) lf[3] = fmaxf(sv[1], 0.f);
+      if (code & 1) lxv[2] = fminf(-(sv[2] - T.mu * (lf[0] + lf[1] + lf[2] + lf[3])), 0.f);
+    }
+    float* lxo = lb + NP + 12 * k + 3 * leg;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) lxo[a] = lxv[a];
+    float* lfo = lb + 24 * N + NP + 16 * k + 4 * leg;
+#pragma unroll
+    for (int f = 0; f < 4; ++f) lfo[f] = lf[f];
+  }
+}
+
+// The driver: one QP instance on this wave (W = 1) or led by it (W > 1).
+template <int NC, int W>
+__device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, int64_t b,
+                                               const Inputs& in, const Outputs& out,
+                                               float* __restrict__ park, TeamSmem<NC, W>* ts,
+                                               int* seq) {
+  // W = 1: the whole lower triangle in this wave's registers; W > 1: this wave's team slots
+  f4 M[TeamCfg<NC, W>::SLOTS];
+  static_assert(W > 1 || TeamCfg<NC, W>::SLOTS == Cfg<NC>::NTL, "W = 1 holds every tile");
+  const int lane = opaque_lane();
+  Diag diag;
+  Instance I;
+  I.b = b;
+  I.N = P.N;
+  I.NP = 12 * P.N;
+  I.T = instance_terrain(P, in, b);
+  diag.poison(W == 1, s.G, 12 * NC, s.v, NC, park, Cfg<NC>::SLAB, lane);
+  CMPC_T0(t_inst);
+  CMPC_CNT(10, 1);
+  stage_instance<NC>(s, P, in, I, lane);
+  // team mode: the gradient's powers of A once per instance (registers to spare: the tiles are
+  // split over the team)
+  // (NC <= 128 only: the larger bins need those registers for their tiles)
+  constexpr bool kPow = W > 1 && NC <= 128;
+  f4 pw_c[4], tw_c[4];
+  if constexpr (kPow) gradient_powers(s, pw_c, tw_c);
+  I.pwc = kPow ? pw_c : nullptr;
+  I.twc = kPow ? tw_c : nullptr;
+  const int n = I.n;
+
+  Ctl c;
+  c.rho = kRhoLow<NC> ? 0.5f * P.rho0 : P.rho0;
+  c.rho_low = kRhoLow<NC>;
+  starting_point<NC>(s, in, I, c.rho, lane);
+  CMPC_ACC(6, t_inst);
+  // ADMM state (x, z, y of triple t at 3t .. 3t+2) lives in LDS, not in registers
+  diag.begin();
+  c.refactor = n > 0;
+  c.nact = n;
+  c.shift = uniformf(P.sigma + c.rho);
+  if (n == 0) c.status = 1;
+  if (n > 0 && in.w_init != nullptr) {
+    // warm active set: the face set of the warm point goes straight to the polish (one
+    // reduced factorization instead of the ADMM one + the polish one); if its KKT check and
+    // repairs fail, the instance restarts as a cold solve (warm_restart)
+    c.warm_session = true;
     WSYNC();
-    float* lb = out.lam + b * (int64_t)(52 * N);
-    for (int o = lane; o < NP; o += 64) {
-      lb[o] = 0.f;                 // lam_x of the states (free)
-      lb[24 * N + o] = -s.L[o];    // lam_a of the dynamics rows
-    }
-    if (lane < 4 * N) {
-      const int k = lane >> 2, leg = lane & 3;
-      const int t = s.tri_of[lane];
-      const float* Bk = Bg + k * 144 + 3 * leg;
-      float sv[3], u[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        u[a] = (t >= 0) ? uf[3 * t + a] : 0.f;
-        float acc = s.R2[3 * leg + a] * u[a];
-#pragma unroll
-        for (int r = 0; r < 12; ++r) acc = fmaf(Bk[r * 12 + a], s.L[12 * k + r], acc);
-        sv[a] = acc;
-      }
-      float lf[4] = {0.f, 0.f, 0.f, 0.f}, lxv[3] = {0.f, 0.f, 0.f};
-      if (t < 0) {  // swing: f = 0 by equal bounds, lam_x = -s
-#pragma unroll
-        for (int a = 0; a < 3; ++a) lxv[a] = -sv[a];
-      } else {
-        int code;
-        if (polished) {
-          code = s.code[t];
-        } else {  // faces the forces lie on, to fp32 rounding
-          const float tz = 1e-5f * fmaxf(u[2], 1.f), lim = T.mu * u[2] - 1e-5f * fmaxf(u[2], 1.f);
-          code = (u[2] <= T.fz_min + tz) ? 1 : 0;
-          code |= (u[0] >= lim) ? 2 : (u[0] <= -lim) ? 4 : 0;
-          code |= (u[1] >= lim) ? 8 : (u[1] <= -lim) ? 16 : 0;
-        }
-        // rows: fx - mu fz, -fx - mu fz, fy - mu fz, -fy - mu fz  (centroidal_mpc.py:332-355)
-        if (code & 2) lf[0] = fmaxf(-sv[0], 0.f);
-        if (code & 4) lf[1] = fmaxf(sv[0], 0.f);
-        if (code & 8) lf[2] = fmaxf(-sv[1], 0.f);
-        if (code & 16) lf[3] = fmaxf(sv[1], 0.f);
-        if (code & 1) lxv[2] = fminf(-(sv[2] - T.mu * (lf[0] + lf[1] + lf[2] + lf[3])), 0.f);
-      }
-      float* lxo = lb + NP + 12 * k + 3 * leg;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) lxo[a] = lxv[a];
-      float* lfo = lb + 24 * N + NP + 16 * k + 4 * leg;
-#pragma unroll
-      for (int f = 0; f < 4; ++f) lfo[f] = lf[f];
-    }
+    if (lane < I.ntri) s.code[lane] = s.pcode[lane];
+    enter_polish<NC>(s, P, I, c);
   }
-  if (lane == 0) {
-#if defined(CMPC_DIAG_COUNTS)  // diagnostic build: iters | attempts | factorizations, cycles / 16
-    out.status[b] = (int)((__builtin_amdgcn_s_memtime() - dg_t0) >> 4);
-    // (flags: 1 loose acceptance, 2 certified face bound missed, 4 a check on a stalled
-    // downdated refinement redone on a fresh factorization)
-    out.iters[b] = iters + 1000 * (dg_pol + 100 * dg_flags) + 1000000 * dg_fact;
-#elif defined(CMPC_DIAG_TIMES)  // start (10 ns ticks, low 31 bits) | duration + 1e9 if teamed
-    out.status[b] = (int)(dt_t0 & 0x7fffffffull);
-    out.iters[b] = (int)(__builtin_amdgcn_s_memrealtime() - dt_t0) ;
-#else
-    out.status[b] = status;
-    out.iters[b] = iters;
-#endif
+  while (n > 0) {
+    if (c.refactor) factorize<NC, W>(s, P, I, c, M, ts, seq, diag, lane);
+    if (c.in_polish) {
+      // (`continue`: round again, to factorize or to refine on a downdated inverse)
+      switch (polish_pass<NC, W>(s, P, I, out, c, M, ts, seq, diag, lane)) {
+        case Polish::kAccepted: accept_point<NC>(s, I, out, c, diag, lane); break;
+        case Polish::kAcceptedLoose: accept_loose<NC>(s, I, out, c, diag, lane); break;
+        case Polish::kRefactorSameSet: refactor_faces<NC>(s, P, I, c, s.dl); continue;
+        case Polish::kRepaired: repair_faces<NC, W>(s, P, I, c, M, lane); continue;
+        case Polish::kWarmRestart: warm_restart<NC>(s, P, I, c); continue;
+        case Polish::kSessionFailed:
+          session_failed<NC, W>(s, P, I, c, M, park, ts, seq, diag, lane);
+          // only a session whose ADMM inverse came back from the park slab goes straight on
+          if (c.refactor) continue;
+          break;
+      }
+      if (c.polished) break;
+    }
+    if (c.it >= P.max_iter) break;
+    c.iters = ++c.it;
+    if (admm_iteration<NC, W>(s, P, I, c, M, ts, seq, lane))
+      start_session<NC, W>(s, P, I, c, M, park, ts, seq, diag, lane);
   }
-  CMPC_CNT(11, iters);
+  if (!c.polished) {
+    if (n > 0) {
+      const bool conv = c.rp <= P.eps_abs + P.eps_rel * c.np_ && c.rd <= P.eps_abs + P.eps_rel * c.nd;
+      c.status = conv ? 2 : -2;
+    }
+    gradient<NC, (W > 1)>(s, P, n, s.z, s.g, I.pwc, I.twc);  // E at u = z (the pure rollout when every leg swings)
+  }
+  TRACEF(b, "END status %d iters %d\n", c.status, c.iters);
+  CMPC_T0(t_out);
+  WSYNC();
+  float* wb = out.w + b * (int64_t)(24 * I.N);
+  if (!write_w<NC>(s, I, wb, c.polished, lane) || !terrain_valid(I.T) || !I.weights_ok)
+    c.status = -10;
+  if (out.y) write_y<NC, W>(s, P, I, out.y + b * (int64_t)I.NP, c.polished, lane);
+  if (out.lam) write_lam<NC>(s, I, out.lam + b * (int64_t)(52 * I.N), c.polished, lane);
+  diag.finish(out.status, out.iters, wb, b, lane, c.status, c.iters);
+  CMPC_CNT(11, c.iters);
   CMPC_ACC(15, t_out);
   CMPC_ACC(5, t_inst);
 }
@@ -2792,7 +2874,7 @@ __device__ __forceinline__ void drain_bin(Smem<NC>& s, const KParams& P, const I
                                           int* seq = nullptr) {
   const int lane = opaque_lane();
   WSYNC();
-  // KParams copies (each bin's Smem layout places them differently); solve_instance overwrites
+  // KParams copies (each bin's Smem layout places them differently); stage_instance overwrites
   // them per instance where Inputs::Q / R are given
   if (lane < 12) {
     s.Q2[lane] = P.Q2[lane];

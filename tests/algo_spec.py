@@ -551,7 +551,7 @@ def solve(inst, p: Params):
 
     failed_starts = []
     # the NC >= 128 bins (nf > 96) start from rho / 2 and return to rho after their first
-    # failed polish session (cmpc_wave.hip solve_instance, rho_low)
+    # failed polish session (cmpc_wave.hip session_failed, Ctl::rho_low)
     # the NC <= 128 bins polish one stable iteration earlier (cmpc_wave.hip CMPC_LIGHT_STABLE_DELTA)
     pstable = max(1, p.stable_checks - (p.light_stable_delta if nf <= 128 else 0))
     rho_low = nf > 96

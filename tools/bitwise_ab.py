@@ -1,6 +1,7 @@
 """A/B of two library builds for bit-identical results: solve the headline batch (config 3,
-65,536) cold and its next tick warm, config 2 at 4,096 cold, with the library given, and write a
-digest of (w, status, iterations); run once per library in separate processes, then compare.
+65,536) cold and its next tick warm, config 2 at 4,096 cold, and small batches that walk the
+paths those miss (small_cases), with the library given, and write (w, status, iterations, and
+y / lam where a case returns them); run once per library in separate processes, then compare.
     python tools/bitwise_ab.py LIB OUT.npz            (GPU)
     python tools/bitwise_ab.py --compare A.npz B.npz   (CPU)"""
 import sys
@@ -10,6 +11,66 @@ import numpy as np
 
 REPO = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(REPO / "convex-mpc-unitree-go2_amd"))
+
+
+GOLDEN = REPO / "tests" / "golden"
+KEYS = ("Ad", "Bd", "gd", "x0", "xref", "contact")
+
+
+def small_cases(res):
+    """Batches of at most ~1,000 instances, seconds each: team mode forced, cmpc_solve_ref, per-robot
+    terrain (one invalid row) and weights, a primal-only warm start, an all-swing instance, N = 8."""
+    import torch
+    from cmpc import Plan, SolverParams, to_device_batch, synth
+
+    def put(tag, r, extra=()):
+        torch.cuda.synchronize()
+        for k, v in zip(("w", "st", "it") + tuple(extra), r):
+            res[f"{tag}_{k}"] = v.cpu().numpy()
+
+    def dev(np_batch):
+        return to_device_batch({k: np.ascontiguousarray(np_batch[k]) for k in KEYS})
+
+    def args(d):
+        return tuple(d[k] for k in KEYS)
+
+    def f32(a):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+
+    plan = Plan(SolverParams(max_batch=4096))
+    # team mode forced, on the fixtures of every bin (y out: the dual writer in team mode)
+    plan.set_team(1 << 40)
+    for name in ("qp_cfg1", "qp_nc192", "qp_hard"):
+        put("team_" + name, plan.solve(*args(dev(np.load(GOLDEN / f"{name}.npz"))), y_out=True), ("y",))
+    plan.set_team(-1)
+    # cmpc_solve_ref on the certified next-tick subset: lam out, then w_init + lam_init in
+    idx = np.load(GOLDEN / "qp_next_tick.npz")["idx"]
+    b1 = synth.make_config(2, B=4096)
+    b2 = synth.next_tick(b1)
+    d1 = dev({k: b1[k][idx] for k in KEYS})
+    d2 = dev({k: b2[k][idx] for k in KEYS})
+    r1 = plan.solve(*args(d1), lam_out=True)
+    put("ref_tick0", r1, ("lam",))
+    put("ref_tick1", plan.solve(*args(d2), w_init=r1[0], lam_init=r1[3], lam_out=True), ("lam",))
+    # a primal-only warm start (w_init without duals), y out
+    put("warm_primal", plan.solve(*args(d2), w_init=r1[0], y_out=True), ("y",))
+    # per-robot mu / fz_min, one invalid row (status -10); per-robot Q / R, one invalid row
+    ft = np.load(GOLDEN / "qp_terrain.npz")
+    mu, fz = ft["mu_A"].copy(), ft["fz_min_A"].copy()
+    mu[3] = -1.0
+    put("terrain", plan.solve(*args(dev(ft)), mu=f32(mu), fz_min=f32(fz), lam_out=True), ("lam",))
+    fw = np.load(GOLDEN / "qp_weights.npz")
+    put("weights", plan.solve(*args(dev(fw)), Q=f32(fw["Q_A"]), R=f32(fw["R_A"]), y_out=True), ("y",))
+    R = fw["R_B"].copy()
+    R[5, 2] = 0.0
+    put("weights_bad_row", plan.solve(*args(dev(fw)), Q=f32(fw["Q_B"]), R=f32(R), lam_out=True), ("lam",))
+    # an all-swing instance among stance ones
+    fc = {k: np.load(GOLDEN / "qp_cfg1.npz")[k].copy() for k in KEYS}
+    fc["contact"][1] = 0
+    put("all_swing", plan.solve(*args(dev(fc)), lam_out=True), ("lam",))
+    # a plan with N = 8
+    p8 = Plan(SolverParams(N=8, max_batch=1024))
+    put("n8", p8.solve(*args(dev(synth.make_batch(768, seed=11, mixed=True, N=8))), y_out=True), ("y",))
 
 
 def run(lib, out):
@@ -34,12 +95,16 @@ def run(lib, out):
         res[tag + "_w"] = w.cpu().numpy()
         res[tag + "_st"] = st.cpu().numpy()
         res[tag + "_it"] = it.cpu().numpy()
+    small_cases(res)
     np.savez_compressed(out, **res)
 
 
 def compare(a, b):
     A, B = np.load(a), np.load(b)
     ok = True
+    if sorted(A.files) != sorted(B.files):
+        print("the two files hold different cases")
+        ok = False
     for k in A.files:
         same = np.array_equal(A[k].view(np.uint32) if A[k].dtype == np.float32 else A[k],
                               B[k].view(np.uint32) if B[k].dtype == np.float32 else B[k])

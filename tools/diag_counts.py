@@ -35,8 +35,8 @@ def main():
         cyc = st.cpu().numpy().astype(np.float64) * 16
         code = it.cpu().numpy().astype(np.int64)
         iters, polraw, fac = code % 1000, (code // 1000) % 1000, code // 1000000
-        # (+100 x flags: 1 loose acceptance, 2 certified face bound missed, 4 accepted on a
-        # stalled downdated refinement -- cmpc_wave.hip solve_instance)
+        # (+100 x flags: 1 loose acceptance, 2 certified face bound missed, 4 a check on a
+        # stalled downdated refinement redone on a fresh factorization -- cmpc_diag.h Diag)
         flags, pol = polraw // 100, polraw % 100
         loose = flags & 1
         if os.environ.get("CMPC_DIAG_SAVE"):
