@@ -5,10 +5,14 @@
 // Team mode gives each QP a workgroup of W waves on W SIMDs of one CU.  Wave 0 (the leader)
 // runs solve_instance's control flow unchanged; waves 1..W-1 (helpers) sit in a command loop and
 // join the leader in the matrix phases, which hold ~70 % of a wave's time:
-//   FACTOR  block-row condensation + 4-pivot block sweep inversion (cmpc_wave.hip 1-2),
-//   SYMV    out = M in,
+//   FACTOR  condensation (closed form, or block-row for a general A) + the 4-pivot block sweep of
+//           every tile into the explicit inverse (team_factor),
+//   SYMV    out = M in (team_symv_part, team_symv_reduce),
 //   PSTORE / PLOAD  park / restore the inverse,
-// each wave on its own share of the lower-triangle tiles, held in its registers.
+// each wave on its own share of the lower-triangle tiles, held in its registers.  (The one-wave
+// kernels keep block LDL' factors instead, cmpc_wave.hip ldl_tiles / ldl_apply.)  The arithmetic
+// of the block-row backward pass and of a pivot block is cmpc_wave.hip's (state_operands,
+// blockrow_*, pivot_block); this file owns the slot loops, the barriers and the read scheduling.
 //
 // Tile ownership: the tile COLUMNS J and TT-1-J form a pair of exactly TT+1 tiles; pair pr goes
 // to wave pr % W as its local pair pr / W.  Local slot l of a pair is tile
@@ -88,7 +92,6 @@ __device__ __forceinline__ void team_sweep_step(Smem<NC>& s, TeamSmem<NC, W>& ts
                                                 int sub, int g, int c) {
   using T = TeamCfg<NC, W>;
   constexpr int TT = T::TT;
-  const bool g1 = g == 1, g2 = g == 2, g3 = g == 3;
   const int c0 = 4 * sub, k0 = 16 * K + c0;
   const int pc = c - c0;
   const bool colw = pc >= 0 && pc < 4, roww = g == sub;
@@ -154,23 +157,8 @@ __device__ __forceinline__ void team_sweep_step(Smem<NC>& s, TeamSmem<NC, W>& ts
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) Dm[i * 4 + jj] = (i == jj) ? rr[i][jj] + 1.f : rr[i][jj];
   }
-  const float i0 = __builtin_amdgcn_rcpf(Dm[0]);
-  const float l10 = Dm[4] * i0, l20 = Dm[8] * i0, l30 = Dm[12] * i0;
-  const float i1 = __builtin_amdgcn_rcpf(Dm[5] - l10 * Dm[4]);
-  const float u21 = Dm[9] - l20 * Dm[4], u31 = Dm[13] - l30 * Dm[4];
-  const float l21 = u21 * i1, l31 = u31 * i1;
-  const float i2 = __builtin_amdgcn_rcpf(Dm[10] - l20 * Dm[8] - l21 * u21);
-  const float u32 = Dm[14] - l30 * Dm[8] - l31 * u21;
-  const float l32 = u32 * i2;
-  const float i3 = __builtin_amdgcn_rcpf(Dm[15] - l30 * Dm[12] - l31 * u31 - l32 * u32);
-  const float n10 = -l10, n21 = -l21, n32 = -l32;
-  const float n20 = l21 * l10 - l20, n31 = l32 * l21 - l31;
-  const float n30 = -l30 - l31 * n10 - l32 * n20;
-  const float w0 = g3 ? n30 : g2 ? n20 : g1 ? n10 : 1.f;
-  const float w1 = g3 ? n31 : g2 ? n21 : g1 ? 1.f : 0.f;
-  const float w2 = g3 ? n32 : g2 ? 1.f : 0.f;
-  const float w3 = g3 ? 1.f : 0.f;
-  const float ig = g3 ? i3 : g2 ? i2 : g1 ? i1 : i0;
+  float w0, w1, w2, w3, ig;
+  pivot_block(Dm, g, w0, w1, w2, w3, ig);
 #pragma unroll
   for (int j = 0; j < T::PPW; ++j) {
     const int pr = w + j * W;
@@ -179,14 +167,12 @@ __device__ __forceinline__ void team_sweep_step(Smem<NC>& s, TeamSmem<NC, W>& ts
     float bj[2];  // b = diag(1/dl) Y' operand of the pair's two columns
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const f4 ph = phj[h];
-      bj[h] = fmaf(w3, ph[3], fmaf(w2, ph[2], fmaf(w1, ph[1], w0 * ph[0]))) * ig;
+      bj[h] = panel_row(phj[h], w0, w1, w2, w3) * ig;
     }
     // padding tiles (I >= TA) are updated too: their panel rows are zero, so is the update
 #pragma unroll
     for (int l = 0; l <= TT; ++l) {
-      const f4 ph = phs[l];
-      const float a = -fmaf(w3, ph[3], fmaf(w2, ph[2], fmaf(w1, ph[1], w0 * ph[0])));
+      const float a = -panel_row(phs[l], w0, w1, w2, w3);
       const float b = (l < TT - pr) ? bj[0] : bj[1];
       M[j * (TT + 1) + l] = mfma4(a, b, M[j * (TT + 1) + l]);
     }
@@ -241,8 +227,9 @@ __device__ __forceinline__ void team_scale(TeamSmem<NC, W>& ts, f4 (&M)[TeamCfg<
 }
 
 // ------------------------------------------------------------------------------------------
-// FACTOR: M <- -(H + diag(Rt) + shift)^-1 share of this wave (block-row condensation, then the
-// 4-pivot block sweep; cmpc_wave.hip condense_tiles_bc / invert_tiles restated per slot)
+// FACTOR: M <- -(H + diag(Rt) + shift)^-1 share of this wave: the closed-form or block-row
+// condensation (cmpc_wave.hip condense_tiles_nil / condense_tiles_bc, per slot; the closed form is
+// restated here, a shared form measured slower), then the 4-pivot block sweep of every owned tile
 // ------------------------------------------------------------------------------------------
 template <int NC, int W, int WV>
 __device__ __forceinline__ void team_factor(Smem<NC>& s, TeamSmem<NC, W>& ts, const KParams& P,
@@ -259,21 +246,12 @@ __device__ __forceinline__ void team_factor(Smem<NC>& s, TeamSmem<NC, W>& ts, co
   n = uniform(n);
 #pragma unroll
   for (int t = 0; t < T::SLOTS; ++t) M[t] = f4{0.f, 0.f, 0.f, 0.f};
-  // State layout (as condense_tiles_fwd and the gradient): accumulator position 4g + q holds
-  // state 3g + q for q < 3 and is padding for q = 3, so every product over the 12 states is
-  // three v_mfma_f32_16x16x4_f32 (K = 12), not four.  Lane column c holds state sc (or none).
-  const int sc = ((c & 3) < 3) ? 3 * (c >> 2) + (c & 3) : -1;
-  float aA[3], aT[3];  // A[sc][3g + q] (A operand of A X), A[3g + q][sc] (of A' X)
-  f4 q2 = {0.f, 0.f, 0.f, 0.f};  // Q2 in accumulator layout
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const int r = 3 * g + q;
-    aA[q] = (sc >= 0) ? s.A[sc * 12 + r] : 0.f;
-    aT[q] = (sc >= 0) ? s.A[r * 12 + sc] : 0.f;
-    q2[q] = (r == sc) ? s.Q2[r] : 0.f;
-  }
+  float aA[3], aT[3];
+  f4 q2;
+  state_operands(s, g, c, aA, aT, q2);  // (cmpc_wave.hip: the K = 12 state layout)
   float* Cs = s.G;  // C_i columns (or V = N b: the closed form), param-major [p][12]
   CMPC_T0(t_f0);
+  const int sc = lane_state(c);
   if (uniform(s.nil)) {
     // ---- closed form for a nilpotent step (cmpc_wave.hip condense_tiles_nil): V = N b by the
     // chunk's wave (J % W), one barrier, then every owned tile is six MFMAs
@@ -370,27 +348,9 @@ __device__ __forceinline__ void team_factor(Smem<NC>& s, TeamSmem<NC, W>& ts, co
       for (int J = 0; J < TT; ++J) {
         if (J % W != w) continue;                        // uniform
         if (16 * J + 15 < p0 || 16 * J >= p1) continue;  // uniform
-        const int p = 16 * J + c;
-        float bt[3];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) bt[q] = s.Bt[p * kBS + 3 * g + q];
-        f4 d = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int q = 0; q < 3; ++q) d = mfma4(Pt[q], (p < n) ? bt[q] : 0.f, d);
-        if (p >= p0 && p < p1) {
-#pragma unroll
-          for (int q = 0; q < 3; ++q) Cs[p * 12 + 3 * g + q] = d[q];
-        }
+        blockrow_C_chunk(s, Cs, Pt, J, p0, p1, n, g, c);
       }
-      if (i > 0) {
-        f4 y = {0.f, 0.f, 0.f, 0.f}, z = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int q = 0; q < 3; ++q) y = mfma4(Pt[q], aT[q], y);
-#pragma unroll
-        for (int q = 0; q < 3; ++q) z = mfma4(aT[q], y[q], z);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) Pt[q] = z[q] + q2[q];
-      }
+      if (i > 0) blockrow_P_step(Pt, aT, q2);
     }
   }
   team_barrier();  // every C_i in LDS
@@ -574,15 +534,11 @@ __device__ __forceinline__ void team_factor(Smem<NC>& s, TeamSmem<NC, W>& ts, co
 
 // ------------------------------------------------------------------------------------------
 // SYMV: this wave's partial sums of out = M in (M symmetric, lower tiles stored).  Row sums of
-// tile (I, J) go to partR[J][rows of chunk I] (each written by the column's owner exactly once),
-// the transposed contributions of the J < I tiles to partC[chunk J].  The leader adds them up
-// after the command's barrier in a fixed order (deterministic).
-// ------------------------------------------------------------------------------------------
-// SYMV: this wave's partial sums of out = M in (M symmetric, lower tiles stored).  Row sums of
 // column pair pr's tiles in row chunk I (both columns' tiles of a row summed before the one
 // 16-lane reduction) go to partR[pr][rows of chunk I], written once by the pair's owner; the
 // transposed contributions of the J < I tiles go to partC[chunk J].  The leader adds them up
 // after the command's barrier in a fixed order (deterministic).
+// ------------------------------------------------------------------------------------------
 template <int NC, int W, int WV>
 __device__ __forceinline__ void team_symv_part(TeamSmem<NC, W>& ts,
                                                const f4 (&M)[TeamCfg<NC, W>::SLOTS], int n,

@@ -13,17 +13,20 @@
 //      tile itself (condense_tiles_fwd); small batches use the block-row form
 //      H_ij = C_i' A^{i-j} B_j, P_i = Q2 + A'P_{i+1}A (condense_tiles_bc).  Lane (g, c) holds
 //      rows 4g..4g+3, column c of every lower-triangle 16x16 tile (f4 per tile, in registers).
-//   2. Invert H + diag(R) + shift in registers by the BLOCK sweep operator, four pivots at a
+//   2. Factor H + diag(R) + shift in registers by the BLOCK sweep operator, four pivots at a
 //      time: S <- S - P^ D^-1 P^' (P^ = the four pivot columns with the pivot block minus I),
 //      then -2 on the four pivot diagonals; the rank-4 update of each tile is ONE MFMA
 //      (A = -Y rows, B = diag(1/dl) Y' columns, Y = P^ L^-T from the 4x4 LDL' of the pivot
-//      block, factored redundantly per lane); pivot columns go through a 4-column LDS panel.
+//      block, factored redundantly per lane: pivot_block); pivot columns go through a 4-column
+//      LDS panel.  Swept only on the tiles right of the pivots, this leaves a block LDL'
+//      factorization (ldl_tiles), applied by two block substitutions (ldl_apply); the team
+//      kernel (cmpc_team.hip) sweeps every tile into the explicit inverse instead.
 //   3. ADMM (OSQP iteration, A = I) on the free forces, lane t owning stance triple t
 //      {fz >= fz_min, |fx| <= mu fz, |fy| <= mu fz} (closed-form projection).  Defect-correction
-//      x-update x~ = x + M(rho(z - x) - grad f(x) - y): M (fp32 inverse) preconditions, grad f
+//      x-update x~ = x + M(rho(z - x) - grad f(x) - y): M (the fp32 factors) preconditions, grad f
 //      comes from the error-coordinate rollout/adjoint (e_{k+1} = A e_k + B_k u_k + d_k).
 //   4. Active-set polish once the face pattern is stable: reduced basis u = T v + t0, condense
-//      + invert again (the ADMM inverse is parked in a per-wave global slab), refine with the
+//      + factor again (the ADMM factors are parked in a per-wave global slab), refine with the
 //      exact gradient, KKT check, primal-dual repairs of the face set.
 //
 // Instances are binned by free-variable count (NC in {96,128,160,192}, a multiple of 16);
@@ -374,6 +377,60 @@ __device__ __forceinline__ void condense_finish(Smem<NC>& s, f4 (&M)[Cfg<NC>::NT
   WSYNC();
 }
 
+// ---- building blocks of the condensations, shared by the one-wave forms below and the team's
+// per-slot form (cmpc_team.hip team_factor) ----
+// K = 12 state layout of every product over the states: position (g, q) of a 16-row chunk holds
+// state 3g + q for q < 3, and q = 3 is padding in every lane group, so the fourth K = 4 slice of
+// each product is all zeros and is skipped: three MFMAs per product instead of four.  The state
+// of output row / lane column c (-1: padding):
+__device__ __forceinline__ int lane_state(int c) {
+  return ((c & 3) < 3) ? 3 * (c >> 2) + (c & 3) : -1;
+}
+// aA = A[sc][3g + q] (A operand of A X), aT = A[3g + q][sc] (of A' X), q2 = Q2 as an
+// accumulator tile (diagonal)
+template <class SM>
+__device__ __forceinline__ void state_operands(SM& s, int g, int c, float (&aA)[3],
+                                               float (&aT)[3], f4& q2) {
+  const int sc = lane_state(c);
+  q2 = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    const int r = 3 * g + q;
+    aA[q] = (sc >= 0) ? s.A[sc * 12 + r] : 0.f;
+    aT[q] = (sc >= 0) ? s.A[r * 12 + sc] : 0.f;
+    q2[q] = (r == sc) ? s.Q2[r] : 0.f;
+  }
+}
+
+// Block-row form, backward pass.  C_i = P_i B_i on column chunk J (P symmetric, so its
+// accumulator layout is also its A-operand layout), stored param-major [p][12] for step i's own
+// params p0 .. p1 - 1
+template <class SM>
+__device__ __forceinline__ void blockrow_C_chunk(SM& s, float* Cs, const f4& Pt, int J, int p0,
+                                                 int p1, int n, int g, int c) {
+  const int p = 16 * J + c;
+  float bt[3];
+#pragma unroll
+  for (int q = 0; q < 3; ++q) bt[q] = s.Bt[p * kBS + 3 * g + q];
+  f4 d = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int q = 0; q < 3; ++q) d = mfma4(Pt[q], (p < n) ? bt[q] : 0.f, d);
+  if (p >= p0 && p < p1) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) Cs[p * 12 + 3 * g + q] = d[q];
+  }
+}
+// P <- Q2 + A' P A
+__device__ __forceinline__ void blockrow_P_step(f4& Pt, const float (&aT)[3], const f4& q2) {
+  f4 y = {0.f, 0.f, 0.f, 0.f}, z = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int q = 0; q < 3; ++q) y = mfma4(Pt[q], aT[q], y);  // Y = P A
+#pragma unroll
+  for (int q = 0; q < 3; ++q) z = mfma4(aT[q], y[q], z);   // Z = A' Y
+#pragma unroll
+  for (int q = 0; q < 4; ++q) Pt[q] = z[q] + q2[q];
+}
+
 template <int NC>
 __device__ __forceinline__ void condense_tiles_fwd(Smem<NC>& s, const KParams& P,
                                                    f4 (&M)[Cfg<NC>::NTL], int n, float shift) {
@@ -384,11 +441,9 @@ __device__ __forceinline__ void condense_tiles_fwd(Smem<NC>& s, const KParams& P
   n = uniform(n);
 #pragma unroll
   for (int t = 0; t < C::NTL; ++t) M[t] = f4{0.f, 0.f, 0.f, 0.f};
-  // State layout: position (g, q) of a 16-row chunk holds state 3g + q for q < 3, and q = 3 is
-  // padding in every lane group, so the fourth K = 4 slice of each product is all zeros and is
-  // skipped: three MFMAs per product instead of four (K = 12 exactly).
-  float aA[3], q2[3];  // A operand of A G: A[state(c)][3g + q]; Q2[3g + q]
-  const int sc = ((c & 3) < 3) ? 3 * (c >> 2) + (c & 3) : -1;  // state of output row c
+  // (Q2 scales the A operand here, as Q2[3g + q], so state_operands' tile form does not apply)
+  float aA[3], q2[3];  // A operand of A G: A[sc][3g + q]; Q2[3g + q]
+  const int sc = lane_state(c);
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
     const int r = 3 * g + q;
@@ -471,23 +526,15 @@ __device__ __forceinline__ void sweep_publish(SM& s, const f4 (&M)[Cfg<NC>::NTL]
   WSYNC();
 }
 
-// LDL of the 4x4 pivot block (rows k0..k0+3 of the panel) and the step's MFMA operands
-template <int NC, int KMIN, class SM>
-__device__ __forceinline__ void sweep_operands(SM& s, int k0, int g, int c,
-                                               float (&a)[Cfg<NC>::TT], float (&b)[Cfg<NC>::TT]) {
-  using C = Cfg<NC>;
-  float Dm[16];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const f4 rrow = *reinterpret_cast<const f4*>(&s.pan[(k0 + i) * 4]);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) Dm[i * 4 + j] = (i == j) ? rrow[j] + 1.f : rrow[j];
-  }
-  f4 ph[C::TT];
-#pragma unroll
-  for (int I = KMIN; I < C::TT; ++I) ph[I] = *reinterpret_cast<const f4*>(&s.pan[(16 * I + c) * 4]);
-  // (inline: factored into a helper returning a struct, the compiler spilled an operand in
-  // every sweep step, 28 scratch stores and loads in the NC <= 128 kernel)
+// LDL' of the 4x4 pivot block Dm (row-major): D = L diag(dl) L' with unit lower L, factored
+// redundantly in every lane, so P^ D^-1 P^' = Y diag(1/dl) Y' with Y = P^ L^-T: the columns of Y
+// are the pivot columns as the scalar sweep would see them (each already eliminated by the earlier
+// pivots of the step), which keeps the scalar sweep's accuracy.  Lane group g takes its row of
+// L^-1 (w0..w3) and ig = 1/dl_g, selected once per step, so each panel row costs four FMAs and no
+// branches (panel_row).  (Results through references: returned as a struct, the compiler spilled
+// an operand in every sweep step, 28 scratch stores and loads in the NC <= 128 kernel.)
+__device__ __forceinline__ void pivot_block(const float (&Dm)[16], int g, float& w0, float& w1,
+                                            float& w2, float& w3, float& ig) {
   const bool g1 = g == 1, g2 = g == 2, g3 = g == 3;
   const float i0 = __builtin_amdgcn_rcpf(Dm[0]);
   const float l10 = Dm[4] * i0, l20 = Dm[8] * i0, l30 = Dm[12] * i0;
@@ -501,14 +548,38 @@ __device__ __forceinline__ void sweep_operands(SM& s, int k0, int g, int c,
   const float n10 = -l10, n21 = -l21, n32 = -l32;
   const float n20 = l21 * l10 - l20, n31 = l32 * l21 - l31;
   const float n30 = -l30 - l31 * n10 - l32 * n20;
-  const float w0 = g3 ? n30 : g2 ? n20 : g1 ? n10 : 1.f;
-  const float w1 = g3 ? n31 : g2 ? n21 : g1 ? 1.f : 0.f;
-  const float w2 = g3 ? n32 : g2 ? 1.f : 0.f;
-  const float w3 = g3 ? 1.f : 0.f;
-  const float ig = g3 ? i3 : g2 ? i2 : g1 ? i1 : i0;
+  w0 = g3 ? n30 : g2 ? n20 : g1 ? n10 : 1.f;
+  w1 = g3 ? n31 : g2 ? n21 : g1 ? 1.f : 0.f;
+  w2 = g3 ? n32 : g2 ? 1.f : 0.f;
+  w3 = g3 ? 1.f : 0.f;
+  ig = g3 ? i3 : g2 ? i2 : g1 ? i1 : i0;
+}
+// y_g = (P^ L^-T)_g = sum_m L^-1[g][m] P^_m of one panel row ph
+__device__ __forceinline__ float panel_row(const f4& ph, float w0, float w1, float w2, float w3) {
+  return fmaf(w3, ph[3], fmaf(w2, ph[2], fmaf(w1, ph[1], w0 * ph[0])));
+}
+
+// The pivot block (rows k0..k0+3 of the panel) and the step's MFMA operands: A = -Y rows,
+// B = diag(1/dl) Y' columns
+template <int NC, int KMIN, class SM>
+__device__ __forceinline__ void sweep_operands(SM& s, int k0, int g, int c,
+                                               float (&a)[Cfg<NC>::TT], float (&b)[Cfg<NC>::TT]) {
+  using C = Cfg<NC>;
+  float Dm[16];  // the panel holds P^ = P - I: add the identity back for D
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const f4 rrow = *reinterpret_cast<const f4*>(&s.pan[(k0 + i) * 4]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) Dm[i * 4 + j] = (i == j) ? rrow[j] + 1.f : rrow[j];
+  }
+  f4 ph[C::TT];
+#pragma unroll
+  for (int I = KMIN; I < C::TT; ++I) ph[I] = *reinterpret_cast<const f4*>(&s.pan[(16 * I + c) * 4]);
+  float w0, w1, w2, w3, ig;
+  pivot_block(Dm, g, w0, w1, w2, w3, ig);
 #pragma unroll
   for (int I = KMIN; I < C::TT; ++I) {
-    const float yg = fmaf(w3, ph[I][3], fmaf(w2, ph[I][2], fmaf(w1, ph[I][1], w0 * ph[I][0])));
+    const float yg = panel_row(ph[I], w0, w1, w2, w3);
     a[I] = -yg;
     b[I] = yg * ig;
   }
@@ -575,6 +646,60 @@ __device__ __forceinline__ void sweep_block(SM& s, f4 (&M)[Cfg<NC>::NTL], int ng
   }
 }
 
+// The plain sweep of the bins above kSweepPipeMaxNC: each 4-pivot step publishes its panel,
+// builds its operands, updates every tile right of the swept pivots and fixes the pivot diagonals.
+// The pivot-block column K is a template constant, so the panel publish, the P^ identity and the
+// diagonal fix address their tiles directly (no runtime dispatch over register tiles); the four
+// 4-pivot steps inside a tile column are a runtime loop.
+template <int NC, int K, class SM>
+__device__ __forceinline__ void sweep_block_plain(SM& s, f4 (&M)[Cfg<NC>::NTL], int ng, int TA,
+                                                  int g, int c) {
+  using C = Cfg<NC>;
+  if constexpr (K < C::TT) {
+    if (4 * K < ng) {  // uniform
+      const int subs = (ng - 4 * K) < 4 ? (ng - 4 * K) : 4;
+      for (int sub = 0; sub < subs; ++sub) {
+        float a[C::TT], b[C::TT];
+        sweep_publish<NC, K>(s, M, sub, g, c);
+        sweep_operands<NC, K>(s, 16 * K + 4 * sub, g, c, a, b);
+        sweep_mfma<NC, -1, false, K>(M, a, b, TA);  // Kc = -1: no tile is critical, so every tile
+        sweep_diagfix<NC, K>(M, sub, g, c);
+      }
+    }
+    sweep_block_plain<NC, K + 1>(s, M, ng, TA, g, c);
+  }
+}
+
+// Diagonal tiles of the block-row and closed-form condensations, which fill only the entries
+// whose column step <= row step: entry (r, c) with step(c) > step(r) is the mirror of (c, r).
+// Each tile turns through a 16 x 16 scratch in the G slab (C and V are dead by then).
+template <int NC>
+__device__ __forceinline__ void mirror_diagonals(Smem<NC>& s, f4 (&M)[Cfg<NC>::NTL], int n, int N) {
+  using C = Cfg<NC>;
+  const int lane = opaque_lane();
+  const int g = lane >> 4, c = lane & 15;
+  WSYNC();
+  float* T = s.G;
+#pragma unroll
+  for (int I = 0; I < C::TT; ++I) {
+    if (16 * I >= n) continue;  // uniform
+    f4 v = M[tile_index(I, I)];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) T[(4 * g + q) * 16 + c] = v[q];
+    WSYNC();
+    const int pc = 16 * I + c;
+    const int kc = (pc < n) ? s.par[pc] : N;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int pr = 16 * I + 4 * g + q;
+      const int kr = (pr < n) ? s.par[pr] : N;
+      if (kc > kr) v[q] = T[c * 16 + 4 * g + q];
+    }
+    M[tile_index(I, I)] = v;
+    WSYNC();
+  }
+}
+
 // Block-row condensation: the lower blocks of the same H are
 //   H[rows of step i, cols of step j <= i] = C_i' A^{i-j} B_j,   C_i = P_i B_i,
 //   P_i = sum_{t >= i} (A^{t-i})' Q2 A^{t-i} = Q2 + A' P_{i+1} A,
@@ -593,18 +718,9 @@ __device__ __forceinline__ void condense_tiles_bc(Smem<NC>& s, const KParams& P,
   n = uniform(n);
 #pragma unroll
   for (int t = 0; t < C::NTL; ++t) M[t] = f4{0.f, 0.f, 0.f, 0.f};
-  // K = 12 state layout (as condense_tiles_fwd): accumulator position 4g + q holds state 3g + q
-  // for q < 3 and is padding for q = 3, so every product over the states is three MFMAs
-  const int sc = ((c & 3) < 3) ? 3 * (c >> 2) + (c & 3) : -1;
-  float aA[3], aT[3];  // A[sc][3g + q] (A operand of A X), A[3g + q][sc] (of A' X)
-  f4 q2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const int r = 3 * g + q;
-    aA[q] = (sc >= 0) ? s.A[sc * 12 + r] : 0.f;
-    aT[q] = (sc >= 0) ? s.A[r * 12 + sc] : 0.f;
-    q2[q] = (r == sc) ? s.Q2[r] : 0.f;
-  }
+  float aA[3], aT[3];
+  f4 q2;
+  state_operands(s, g, c, aA, aT, q2);
   float* Cs = s.G;  // C_i columns, param-major [p][12] (the G slab is free while condensing)
   // ---- backward: P_i and C_i = P_i B_i for i = N-1 .. 0 ----
   f4 Pt = q2;  // P_{N-1} = Q2 (diagonal)
@@ -614,27 +730,9 @@ __device__ __forceinline__ void condense_tiles_bc(Smem<NC>& s, const KParams& P,
 #pragma unroll
     for (int J = 0; J < C::TT; ++J) {
       if (16 * J + 15 < p0 || 16 * J >= p1) continue;  // uniform: chunks holding step i's params
-      const int p = 16 * J + c;
-      float bt[3];
-#pragma unroll
-      for (int q = 0; q < 3; ++q) bt[q] = (p < n) ? s.Bt[p * kBS + 3 * g + q] : 0.f;
-      f4 d = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int q = 0; q < 3; ++q) d = mfma4(Pt[q], bt[q], d);  // C = P B (P symmetric)
-      if (p >= p0 && p < p1) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) Cs[p * 12 + 3 * g + q] = d[q];
-      }
+      blockrow_C_chunk(s, Cs, Pt, J, p0, p1, n, g, c);
     }
-    if (i > 0) {  // P_{i-1} = Q2 + A' P_i A
-      f4 y = {0.f, 0.f, 0.f, 0.f}, z = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int q = 0; q < 3; ++q) y = mfma4(Pt[q], aT[q], y);   // Y = P A
-#pragma unroll
-      for (int q = 0; q < 3; ++q) z = mfma4(aT[q], y[q], z);    // Z = A' Y
-#pragma unroll
-      for (int q = 0; q < 4; ++q) Pt[q] = z[q] + q2[q];
-    }
+    if (i > 0) blockrow_P_step(Pt, aT, q2);
   }
   WSYNC();
   // ---- forward: G_t = A G_{t-1} + new columns; rows of step t += C_t' G_t ----
@@ -683,27 +781,7 @@ __device__ __forceinline__ void condense_tiles_bc(Smem<NC>& s, const KParams& P,
       }
     }
   }
-  // ---- diagonal tiles: entry (r, c) with step(c) > step(r) is the mirror of (c, r) ----
-  WSYNC();
-  float* T = s.G;  // 16 x 16 scratch per tile
-#pragma unroll
-  for (int I = 0; I < C::TT; ++I) {
-    if (16 * I >= n) continue;  // uniform
-    f4 v = M[tile_index(I, I)];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) T[(4 * g + q) * 16 + c] = v[q];
-    WSYNC();
-    const int pc = 16 * I + c;
-    const int kc = (pc < n) ? s.par[pc] : N;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int pr = 16 * I + 4 * g + q;
-      const int kr = (pr < n) ? s.par[pr] : N;
-      if (kc > kr) v[q] = T[c * 16 + 4 * g + q];
-    }
-    M[tile_index(I, I)] = v;
-    WSYNC();
-  }
+  mirror_diagonals<NC>(s, M, n, N);
   condense_finish<NC>(s, M, n, shift);
 }
 
@@ -823,27 +901,7 @@ __device__ __forceinline__ void condense_tiles_nil(Smem<NC>& s, const KParams& P
       M[tile_index(I, J)] = acc;
     }
   }
-  // diagonal tiles: entry (r, c) with step(c) > step(r) is the mirror of (c, r)
-  WSYNC();
-  float* T = s.G;  // 16 x 16 scratch per tile (V is dead)
-#pragma unroll
-  for (int I = 0; I < C::TT; ++I) {
-    if (I >= TA) continue;  // uniform
-    f4 v = M[tile_index(I, I)];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) T[(4 * g + q) * 16 + c] = v[q];
-    WSYNC();
-    const int pc = 16 * I + c;
-    const int kc = (pc < n) ? s.par[pc] : N;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int pr = 16 * I + 4 * g + q;
-      const int kr = (pr < n) ? s.par[pr] : N;
-      if (kc > kr) v[q] = T[c * 16 + 4 * g + q];
-    }
-    M[tile_index(I, I)] = v;
-    WSYNC();
-  }
+  mirror_diagonals<NC>(s, M, n, N);
   condense_finish<NC>(s, M, n, shift);
 }
 
@@ -876,7 +934,7 @@ __device__ __forceinline__ bool nilpotent_step(SM& s) {
 // has ~25 % fewer MFMAs but longer dependency chains.  With one wave per SIMD (small batches,
 // latency) the chains are what a wave waits on either way and the fewer MFMAs win (B = 256:
 // 0.61 -> 0.48 ms); with two busy waves per SIMD the forward form keeps the matrix pipe ~80 %
-// busy and is ~5 % faster (tools/phase_bench.hip).
+// busy and is ~5 % faster.
 template <int NC>
 __device__ __forceinline__ void condense_tiles(Smem<NC>& s, const KParams& P,
                                                f4 (&M)[Cfg<NC>::NTL], int n, float shift,
@@ -942,88 +1000,7 @@ __device__ __forceinline__ void ldl_tiles(SM& s, f4 (&M)[Cfg<NC>::NTL], int n) {
       sweep_block<NC, 0>(s, M, ng, TA, g, c, a, b);
     }
   } else {
-  const bool g1 = g == 1, g2 = g == 2, g3 = g == 3;
-  // The pivot-block column K is a compile-time constant of the outer (unrolled) loop, so the
-  // panel publish, the P^ identity and the diagonal fix address their tiles directly (no
-  // runtime dispatch over register tiles); the four 4-pivot steps inside a tile column are a
-  // runtime loop.
-#pragma unroll
-  for (int K = 0; K < C::TT; ++K) {
-    if (4 * K >= ng) continue;  // uniform; `continue` keeps the unrolled loop's tiles static
-    const int subs = (ng - 4 * K) < 4 ? (ng - 4 * K) : 4;
-    for (int sub = 0; sub < subs; ++sub) {
-      const int c0 = 4 * sub, k0 = 16 * K + c0;
-      const int pc = c - c0;
-      const bool colw = pc >= 0 && pc < 4, roww = g == sub;
-      // publish the 4 pivot columns (P^ = P - I on the pivot rows) as panel rows [row][0..3]
-      // from tiles (I >= K, K) (the factorization never reads the swept rows above the block)
-      if (colw) {
-#pragma unroll
-        for (int I = K; I < C::TT; ++I) {
-          f4 m = M[tile_index(I, K)];
-          if (I == K) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) m[q] -= (4 * g + q == c) ? 1.f : 0.f;
-          }
-#pragma unroll
-          for (int q = 0; q < 4; ++q) s.pan[(16 * I + 4 * g + q) * 4 + pc] = m[q];
-        }
-      }
-      WSYNC();
-      // D = L diag(dl) L' (unit lower L), so P^ D^-1 P^' = Y diag(1/dl) Y' with Y = P^ L^-T: the
-      // columns of Y are the pivot columns as the scalar sweep would see them (each already
-      // eliminated by the earlier pivots of the step), which keeps the scalar sweep's accuracy.
-      float Dm[16];  // the panel holds P^ = P - I: add the identity back for D
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const f4 rrow = *reinterpret_cast<const f4*>(&s.pan[(k0 + i) * 4]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) Dm[i * 4 + j] = (i == j) ? rrow[j] + 1.f : rrow[j];
-      }
-      const float i0 = __builtin_amdgcn_rcpf(Dm[0]);
-      const float l10 = Dm[4] * i0, l20 = Dm[8] * i0, l30 = Dm[12] * i0;
-      const float i1 = __builtin_amdgcn_rcpf(Dm[5] - l10 * Dm[4]);
-      const float u21 = Dm[9] - l20 * Dm[4], u31 = Dm[13] - l30 * Dm[4];
-      const float l21 = u21 * i1, l31 = u31 * i1;
-      const float i2 = __builtin_amdgcn_rcpf(Dm[10] - l20 * Dm[8] - l21 * u21);
-      const float u32 = Dm[14] - l30 * Dm[8] - l31 * u21;
-      const float l32 = u32 * i2;
-      const float i3 = __builtin_amdgcn_rcpf(Dm[15] - l30 * Dm[12] - l31 * u31 - l32 * u32);
-      // y_g = (P^ L^-T)_g = sum_m L^-1[g][m] P^_m: this lane's row of L^-1 (unit lower) and
-      // 1/dl_g, selected once per step, so each panel row costs four FMAs and no branches
-      const float n10 = -l10, n21 = -l21, n32 = -l32;
-      const float n20 = l21 * l10 - l20, n31 = l32 * l21 - l31;
-      const float n30 = -l30 - l31 * n10 - l32 * n20;
-      const float w0 = g3 ? n30 : g2 ? n20 : g1 ? n10 : 1.f;
-      const float w1 = g3 ? n31 : g2 ? n21 : g1 ? 1.f : 0.f;
-      const float w2 = g3 ? n32 : g2 ? 1.f : 0.f;
-      const float w3 = g3 ? 1.f : 0.f;
-      const float ig = g3 ? i3 : g2 ? i2 : g1 ? i1 : i0;
-      const int KM = K;  // (a constant once the K loop is unrolled)
-      float a[C::TT], b[C::TT];
-#pragma unroll
-      for (int I = KM; I < C::TT; ++I) {
-        const f4 ph = *reinterpret_cast<const f4*>(&s.pan[(16 * I + c) * 4]);
-        const float yg = fmaf(w3, ph[3], fmaf(w2, ph[2], fmaf(w1, ph[1], w0 * ph[0])));
-        a[I] = -yg;
-        b[I] = yg * ig;
-      }
-#pragma unroll
-      for (int I = KM; I < C::TT; ++I) {
-        if (I >= TA) continue;  // uniform
-#pragma unroll
-        for (int J = KM; J <= I; ++J) {
-          const int t = tile_index(I, J);
-          M[t] = mfma4(a[I], b[J], M[t]);
-        }
-      }
-      {  // -2 on the 4 pivot diagonals
-        f4& m = M[tile_index(K, K)];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) m[q] -= (roww && pc == q) ? 2.f : 0.f;
-      }
-    }
-  }
+    sweep_block_plain<NC, 0>(s, M, ng, TA, g, c);
   }
   // undo the scaling: the diagonal tiles hold -(scaled D_K^-1), the tiles below them the
   // scaled L~ = S^-1 L S

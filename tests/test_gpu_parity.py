@@ -256,6 +256,32 @@ def test_general_step_matrix(plan, reps):
         assert rel_err_U(w[i * reps:i * reps + 1], wr[None])[0] <= TOL_U, i
 
 
+def test_general_step_matrix_one_wave_latency():
+    """The same eight damped instances (free-force counts 96 .. 150: bins NC 96, 128, 144, 160)
+    with team mode off: a small batch then runs one wave per QP in latency mode, where the NC 96 /
+    128 kernel condenses a general A by the block-row form (cmpc_wave.hip condense_tiles_bc), which
+    the default team rule never reaches.  Both group kernels must be the ones launched.  The
+    small-batch rule of parity_util.assert_verified (at most one status 2) and test_gpu_terrain's
+    bars: status 1 within 1e-4 of the certified optimum, status 2 within 1e-3."""
+    from cmpc import Plan, SolverParams, solve_batch, synth
+    b = synth.make_config(2, B=8)
+    for r in range(3, 6):
+        b["Ad"][:, r, r] = 0.999
+    Nm = b["Ad"][0].astype(np.float32) - np.eye(12, dtype=np.float32)
+    assert np.any(Nm @ Nm != 0)
+    p = Plan(SolverParams(max_batch=16))
+    p.set_team(0)
+    names = p.solve_kernels(8)
+    assert names[0] and names[1] and all("group" in k for k in names[:2]), names
+    w, st, it = solve_batch({k: b[k] for k in ("Ad", "Bd", "gd", "x0", "xref", "contact")}, plan=p)
+    print("status", st.tolist(), "iters", it.tolist())
+    ok = assert_verified(st)
+    errs = [rel_err_U(w[i:i + 1], _tight(b, i)[None])[0] for i in range(8)]
+    print("rel err", errs)
+    for i in range(8):
+        assert errs[i] <= (TOL_U if ok[i] else 1e-3), (i, int(st[i]), errs[i])
+
+
 def test_general_step_matrix_heavy_bins(plan):
     """The general-A path (the squared-power gradient scans and forward condensation, fp32
     rollout) on the NC 144 / 160 / 192 kernels and the hard instances (face-downdate repairs):

@@ -147,8 +147,10 @@ def test_team_park_restore_paths(team_plan):
 
 @pytest.mark.parametrize("name", ["qp_cfg1.npz", "qp_cfg2.npz", "qp_nc192.npz"])
 def test_one_wave_latency_mode_parity(wave_plan, name):
-    """With team mode off, small batches run one wave per QP in latency mode (block-row
-    condensation for NC <= 128): same parity bar."""
+    """With team mode off, small batches run one wave per QP in latency mode: same parity bar.
+    The fixtures' step matrix is nilpotent, so every bin condenses by the closed form
+    (condense_tiles_nil); the block-row form that latency mode selects for a general A on NC <= 128
+    is covered by test_gpu_parity.py::test_general_step_matrix_one_wave_latency."""
     from cmpc import solve_batch
     fx = load_fixture(name)
     w, st, it = solve_batch(fixture_batch(fx), plan=wave_plan)

@@ -19,7 +19,8 @@ KEYS = ("Ad", "Bd", "gd", "x0", "xref", "contact")
 
 def small_cases(res):
     """Batches of at most ~1,000 instances, seconds each: team mode forced, cmpc_solve_ref, per-robot
-    terrain (one invalid row) and weights, a primal-only warm start, an all-swing instance, N = 8."""
+    terrain (one invalid row) and weights, a primal-only warm start, an all-swing instance, N = 8,
+    and a general step matrix in every mode (general_cases: the fixtures above are all nilpotent)."""
     import torch
     from cmpc import Plan, SolverParams, to_device_batch, synth
 
@@ -71,6 +72,39 @@ def small_cases(res):
     # a plan with N = 8
     p8 = Plan(SolverParams(N=8, max_batch=1024))
     put("n8", p8.solve(*args(dev(synth.make_batch(768, seed=11, mixed=True, N=8))), y_out=True), ("y",))
+    general_cases(plan, put, dev, args)
+
+
+def damped(b):
+    """The attitude-damped step matrix of tests/test_gpu_parity.py::test_general_step_matrix: not
+    I + N with N^2 = 0, so the solve takes the general condensations and gradient."""
+    b = {k: np.array(b[k], dtype=np.float64) for k in KEYS}
+    for r in range(3, 6):
+        b["Ad"][:, r, r] = 0.999
+    return b
+
+
+def general_cases(plan, put, dev, args):
+    """General (non-nilpotent) step matrix, every bin.  Team forced: the team kernel's general
+    branch.  Team off at B <= 4 x CUs: latency mode, block-row condensation on NC 96 / 128 and
+    forward condensation on the heavier bins.  gen_heavy x 40 (1,280 > 4 x CUs) under the default
+    rule: throughput mode, forward condensation everywhere, plain sweep on NC 144 / 160 / 192."""
+    from cmpc import synth
+    # free-force counts 96, 105, 120, 150, 126, 132, 147, 96: bins NC 96, 128, 144 and 160, with
+    # partial last pivot blocks (105 -> 27 pivot groups, 150 -> 38)
+    gen8 = damped(synth.make_config(2, B=8))
+    # test_general_step_matrix_heavy_bins' 32 instances: 12 cfg2 fixtures with n in 129..150, 16
+    # of qp_nc192.npz (n 162 / 165) and the 4 of qp_hard.npz
+    c2, c192, hd = (np.load(GOLDEN / f"{f}.npz") for f in ("qp_cfg2", "qp_nc192", "qp_hard"))
+    heavy = np.flatnonzero(3 * (c2["contact"] != 0).reshape(len(c2["contact"]), -1).sum(1) > 128)[:12]
+    gen_heavy = damped({k: np.concatenate([c2[k][heavy], c192[k][:16], hd[k]]) for k in KEYS})
+    for tag, b, modes in (("gen8", gen8, (("team", 1 << 40, 1), ("wave", 0, 1), ("auto", -1, 1))),
+                          ("gen_heavy", gen_heavy, (("team", 1 << 40, 1), ("wave", 0, 1), ("x40", -1, 40)))):
+        for mode, team, reps in modes:
+            plan.set_team(team)
+            d = dev({k: np.repeat(b[k], reps, axis=0) for k in KEYS})
+            put(f"{tag}_{mode}", plan.solve(*args(d), y_out=True), ("y",))
+    plan.set_team(-1)
 
 
 def run(lib, out):

@@ -50,7 +50,8 @@ def main():
             continue
         short = re.sub(r"\(.*\)$", "", dn).replace("cmpc::", "")
         print(f"{short:46s} vgpr {k.get('vgpr_count'):>4} agpr {k.get('agpr_count'):>4} "
-              f"vgpr_spill {k.get('vgpr_spill_count'):>5} lds {k.get('group_segment_fixed_size'):>6} "
+              f"vgpr_spill {k.get('vgpr_spill_count'):>5} sgpr_spill {k.get('sgpr_spill_count'):>5} "
+              f"lds {k.get('group_segment_fixed_size'):>6} "
               f"scratch {k.get('private_segment_fixed_size'):>5}")
 
 
