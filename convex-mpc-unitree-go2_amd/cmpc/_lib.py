@@ -55,8 +55,19 @@ class CSolveIO(ctypes.Structure):
                   "lam_init", "w_out", "y_out", "lam_out", "status", "iters", "Q", "R")])
 
 
+class CKktIO(ctypes.Structure):
+    """cmpc_kkt_io (include/cmpc.h): a batch of points to evaluate, with the per-instance values
+    of CSolveIO.  ``size`` is this mirror's sizeof."""
+    _fields_ = ([("size", ctypes.c_uint32)] +
+                [(n, ctypes.c_void_p) for n in
+                 ("Ad", "Bd", "gd", "x0", "xref", "contact", "mu", "fz_min", "Q", "R", "w", "lam")] +
+                [("face_tol", ctypes.c_float), ("res", ctypes.c_void_p)])
+
+
+KKT_COLUMNS = ("cost", "stat", "prim", "comp")  # CMPC_KKT_COST .. CMPC_KKT_COMP
+
 EXPORTS = ("cmpc_params_default", "cmpc_plan_create", "cmpc_solve", "cmpc_plan_destroy",
-           "cmpc_build_dynamics", "cmpc_solve_warm", "cmpc_solve_ref", "cmpc_solve_io_run", "cmpc_generate_traj", "cmpc_leg_torque", "cmpc_srb_step",
+           "cmpc_build_dynamics", "cmpc_solve_warm", "cmpc_solve_ref", "cmpc_solve_io_run", "cmpc_kkt_run", "cmpc_generate_traj", "cmpc_leg_torque", "cmpc_srb_step",
            "cmpc_plan_set_timing", "cmpc_plan_timing_read", "cmpc_plan_set_team", "cmpc_plan_team_batch",
            "cmpc_plan_set_heavy_first",
            "cmpc_plan_heavy_first_batch", "cmpc_plan_solve_kernel", "cmpc_plan_stats",
@@ -102,6 +113,9 @@ def load(path: str | Path | None = None) -> ctypes.CDLL:
     if hasattr(lib, "cmpc_solve_io_run"):  # absent from builds that predate per-instance terrain
         lib.cmpc_solve_io_run.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(CSolveIO), vp]
         lib.cmpc_solve_io_run.restype = ctypes.c_int
+    if hasattr(lib, "cmpc_kkt_run"):  # absent from builds that predate the device-side KKT check
+        lib.cmpc_kkt_run.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(CKktIO), vp]
+        lib.cmpc_kkt_run.restype = ctypes.c_int
     lib.cmpc_build_dynamics.argtypes = [vp, ctypes.c_int64, ctypes.c_float] + [vp] * 8
     lib.cmpc_build_dynamics.restype = ctypes.c_int
     if hasattr(lib, "cmpc_generate_traj"):

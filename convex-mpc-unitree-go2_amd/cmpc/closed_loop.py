@@ -47,12 +47,18 @@ class ClosedLoop:
 
     ``Q`` / ``R``: per-robot cost weights, (B, 12) or (12,) values (None: the plan's constants),
     kept the same way as the device tensors ``self.Q`` / ``self.R``: a supervisor that writes a
-    robot's row in place re-weights that robot from the next tick on."""
+    robot's row in place re-weights that robot from the next tick on.
+
+    ``report=True``: every tick also evaluates the returned forces on the device (``Plan.kkt``
+    with recovered multipliers, the loop's ``mu`` / ``fz_min`` / ``Q`` / ``R``) into ``self.kkt``,
+    a (B, 4) float64 tensor with the columns ``cmpc.KKT_COLUMNS``: a per-robot health signal
+    besides ``status``.  ``self.x_solve`` holds the state the tick solved from (the plant
+    overwrites ``x``).  Both run on the tick's stream, so a captured graph carries them."""
 
     def __init__(self, B: int, plan: Optional[Plan] = None, gait_hz: float = synth.GAIT_HZ,
                  duty: float = synth.GAIT_DUTY, offsets=synth.TROT_OFFSETS, nsub: int = 20,
                  seed: int = 0, device="cuda", shift_warm: bool = True, mu=None, fz_min=None,
-                 Q=None, R=None):
+                 Q=None, R=None, report: bool = False):
         self.plan = plan or Plan(SolverParams(max_batch=B))
         self.B, self.N = B, self.plan.params.N
         dev = torch.device(device)
@@ -105,6 +111,10 @@ class ClosedLoop:
             None if v is None else
             torch.as_tensor(v, dtype=f32).expand(B, 12).contiguous().to(dev, copy=True)
             for v in (Q, R))
+        self.report = bool(report)
+        if self.report:
+            self.x_solve = torch.empty_like(self.x)
+            self.kkt = torch.empty((B, 4), dtype=f64, device=dev)
         self.shift_warm = shift_warm
         self.warm = False
         self.graph = None
@@ -137,9 +147,14 @@ class ClosedLoop:
             kw = dict(w_init=self.w_init, y_init=self.y_init)
         else:
             kw = dict(w_init=self.w, y_init=self.y) if warm else {}
+        if self.report:
+            self.x_solve.copy_(self.x)
         p.solve(self.Ad, self.Bd, self.gd, self.x, self.xref, self.ct,
                 out=(self.w, self.status, self.iters), stream=stream, y_out=self.y,
                 mu=self.mu, fz_min=self.fz_min, Q=self.Q, R=self.R, **kw)
+        if self.report:
+            p.kkt(self.Ad, self.Bd, self.gd, self.x_solve, self.xref, self.ct, self.w,
+                  mu=self.mu, fz_min=self.fz_min, Q=self.Q, R=self.R, out=self.kkt, stream=stream)
         sp = ctypes.c_void_p(stream.cuda_stream)
         P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
         force = self.w[:, 12 * N:]                        # U[:, 0] rows (test_MPC.py:196)

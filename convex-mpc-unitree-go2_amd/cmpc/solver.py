@@ -17,6 +17,7 @@ from . import _lib
 
 STATUS_STRINGS = {1: "solved", 2: "solved inaccurate", -2: "maximum iterations reached",
                   -10: "unsolved"}
+KKT_COLUMNS = _lib.KKT_COLUMNS   # the columns of Plan.kkt's result
 
 
 @dataclass
@@ -331,6 +332,56 @@ class Plan:
             rc = self.lib.cmpc_solve_io_run(self._h, ctypes.c_int64(B), ctypes.byref(io), sp)
         _check(self.lib, rc, "cmpc_solve_io_run")
         return outs + ((y_out,) if ret_y else ()) + ((lam_out,) if ret_l else ())
+
+    def kkt(self, Ad, Bd, gd, x0, xref, contact, w, lam=None, mu=None, fz_min=None, Q=None,
+            R=None, face_tol=None, out=None, stream=None):
+        """Cost and KKT residuals of B points on the device (cmpc_kkt_run, include/cmpc.h).
+
+        ``Ad`` .. ``contact`` and ``mu`` / ``fz_min`` / ``Q`` / ``R`` as for :meth:`solve`; ``w``
+        (B, 24N) fp32 the points (a solve's w); ``lam`` (B, 52N) fp32 their multipliers in the
+        reference layout (a solve's ``lam_out``), or None to recover them from ``w`` on the
+        device (the rule of :func:`cmpc.duals.recover` with ``tol = face_tol``, None = 1e-6):
+        the mode for a plain or warm solve's output.  Returns a (B, 4) float64 device tensor
+        with the columns :data:`KKT_COLUMNS`: the reference's cost 1/2 w'Hw + g'w and the
+        stationarity, primal and complementarity residuals of ``oracle.mpc_qp.kkt_residuals``
+        (``comp`` is +inf when a multiplier has the sign of an infinite bound).  An instance
+        with an invalid mu / fz_min entry or Q / R row gets four NaNs.  Asynchronous on
+        ``stream`` (default: torch's current stream), no allocation when ``out`` is given,
+        graph-capturable; the inputs are not modified and B is not limited by max_batch."""
+        if not hasattr(self.lib, "cmpc_kkt_run"):
+            raise CmpcError("cmpc: this libcmpc.so has no cmpc_kkt_run: Plan.kkt needs a library "
+                            "built from sources that declare it")
+        N = self.params.N
+        B = Ad.shape[0]
+        if B < 1:
+            raise ValueError("kkt needs at least one instance")
+        f32 = torch.float32
+        io = _lib.CKktIO()
+        io.size = ctypes.sizeof(_lib.CKktIO)
+        req = dict(Ad=(Ad, f32, (B, 12, 12)), Bd=(Bd, f32, (B, N, 12, 12)), gd=(gd, f32, (B, 12)),
+                   x0=(x0, f32, (B, 12)), xref=(xref, f32, (B, N, 12)),
+                   contact=(contact, torch.uint8, (B, 4, N)), w=(w, f32, (B, 24 * N)))
+        opt = dict(lam=(lam, f32, (B, 52 * N)), mu=(mu, f32, (B,)), fz_min=(fz_min, f32, (B,)),
+                   Q=(Q, f32, (B, 12)), R=(R, f32, (B, 12)))
+        for name, (t, dtype, shape) in {**req, **opt}.items():
+            if t is None and name in opt:
+                continue
+            _dev_tensor(t, name, dtype, shape)
+            self._same_device(t)
+            setattr(io, name, t.data_ptr())
+        if out is None:
+            out = torch.empty((B, 4), dtype=torch.float64, device=Ad.device)
+        _dev_tensor(out, "out", torch.float64, (B, 4))
+        self._same_device(out)
+        io.res = out.data_ptr()
+        io.face_tol = 0.0 if face_tol is None else float(face_tol)
+        if stream is None:
+            stream = torch.cuda.current_stream(Ad.device)
+        sp = ctypes.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else stream)
+        with torch.cuda.device(Ad.device):
+            rc = self.lib.cmpc_kkt_run(self._h, ctypes.c_int64(B), ctypes.byref(io), sp)
+        _check(self.lib, rc, "cmpc_kkt_run")
+        return out
 
     def build_dynamics(self, mass, inertia, r_feet, xref, dt, out=None, stream=None):
         """Discrete dynamics (Ad, Bd, gd) of B robots on the device -- the reference's

@@ -222,6 +222,60 @@ typedef struct cmpc_solve_io {
 
 int cmpc_solve_io_run(cmpc_plan* plan, int64_t B, const cmpc_solve_io* io, void* stream);
 
+/* Cost and KKT residuals of B points of the QP, on the device: how good is each answer of a
+ * batch.  Evaluates, for every instance, the reference QP that Ad..contact and the instance's
+ * Q, R, mu, fz_min define (H = diag(2Q.., 2R..), g = [-2Q xref; 0], A = [dynamics rows; friction
+ * rows], the bounds of centroidal_mpc.py:122-176, 255-283) at the point w with the multipliers
+ * lam, in CasADi's convention  H w + g + A' lam_a + lam_x = 0,  lam > 0 only on an active upper
+ * and lam < 0 only on an active lower bound:
+ *   res[b][CMPC_KKT_COST]  1/2 w'Hw + g'w  (the reference's sol["cost"])
+ *   res[b][CMPC_KKT_STAT]  max |H w + g + A' lam_a + lam_x|
+ *   res[b][CMPC_KKT_PRIM]  the largest violation of lba <= A w <= uba and lbx <= w <= ubx
+ *   res[b][CMPC_KKT_COMP]  the largest  max(lam, 0) |ub - v|  or  max(-lam, 0) |v - lb|  over the
+ *                          bounds on v = w (lam_x) and v = A w (lam_a); +inf when a multiplier
+ *                          has the sign of an infinite bound (a positive friction multiplier on a
+ *                          swing leg, a nonzero lam_x on a state)
+ * All arithmetic is fp64 on the fp32 inputs widened exactly; each sum runs in a fixed order, so
+ * the results are bitwise repeatable and do not depend on B or on the instance's place in the
+ * batch.  Nonzero contact entries are stance.
+ *   w    [B][24N]  fp32  the point, in w_out's layout (not modified)
+ *   lam  [B][52N]  fp32  nullable; [lam_x | lam_a] in the layout of cmpc_solve_ref's lam_out.
+ *                        NULL: the multipliers are first recovered from w on the device (fp64):
+ *                        the dynamics rows' from the backward adjoint of the rollout, the
+ *                        friction and fz_min multipliers from the faces w's forces hold (a force
+ *                        is on a face within face_tol x max(1, |fz|)), a swing force's
+ *                        lam_x = -(2R u - Bd' lam_eq).  STAT is then the stationarity left on
+ *                        the free force directions, which the solver's status-1 certificate
+ *                        does not bound.  This is the mode for the w_out of a solve.
+ *   mu, fz_min, Q, R     nullable per-instance values, as in the struct cmpc_solve_io: NULL,
+ *                        or rows filled with the plan's constants, give bit for bit the same.
+ *                        An instance whose entry is invalid by that struct's rules gets four
+ *                        NaNs; it never fails the call and the other instances are unaffected.
+ *   face_tol             used when lam == NULL; 0 selects 1e-6.  Negative or not finite:
+ *                        CMPC_E_INVALID.
+ *   res  [B][4]    fp64  out
+ * `size` is the caller's sizeof of the struct (fields past it read as NULL or 0); it must reach
+ * past `res`.  B >= 1; no workspace is used, so the plan's max_batch does not limit B.  Same
+ * guarantees as cmpc_solve: asynchronous on `stream`, no allocation, no host synchronisation,
+ * graph-capturable; the plan's device must be current. */
+typedef struct cmpc_kkt_io {
+  uint32_t size;            /* sizeof of this struct in the caller's header */
+  const float *Ad, *Bd, *gd, *x0, *xref;  /* as cmpc_solve */
+  const uint8_t* contact;
+  const float *mu, *fz_min; /* [B] nullable: the plan's constants */
+  const float *Q, *R;       /* [B][12] nullable */
+  const float* w;           /* [B][24N] the point to evaluate (a w_out) */
+  const float* lam;         /* [B][52N] nullable: [lam_x | lam_a] */
+  float face_tol;           /* used when lam == NULL; 0 selects 1e-6 */
+  double* res;              /* [B][4] out: cost, stat, prim, comp */
+} cmpc_kkt_io;
+
+#define CMPC_KKT_COST 0
+#define CMPC_KKT_STAT 1
+#define CMPC_KKT_PRIM 2
+#define CMPC_KKT_COMP 3
+int cmpc_kkt_run(cmpc_plan* plan, int64_t B, const cmpc_kkt_io* io, void* stream);
+
 void cmpc_plan_destroy(cmpc_plan* plan);
 
 /* QP data on the device: the reference's discrete dynamics
