@@ -64,10 +64,25 @@ class CKktIO(ctypes.Structure):
                 [("face_tol", ctypes.c_float), ("res", ctypes.c_void_p)])
 
 
+class CGainIO(ctypes.Structure):
+    """cmpc_gain_io (include/cmpc.h): a batch whose feedback gain and value function are wanted,
+    with the per-instance values of CSolveIO.  ``size`` is this mirror's sizeof."""
+    _fields_ = ([("size", ctypes.c_uint32)] +
+                [(n, ctypes.c_void_p) for n in
+                 ("Ad", "Bd", "gd", "x0", "xref", "contact", "mu", "fz_min", "Q", "R", "w",
+                  "faces")] +
+                [("face_tol", ctypes.c_float)] +
+                [(n, ctypes.c_void_p) for n in ("K", "Vx", "Vxx", "u_star", "faces_out")])
+
+
+# cmpc_gain_io's face-mask bits of a stance (step, leg): CMPC_FACE_*
+FACE_FZ_MIN, FACE_FX_POS, FACE_FX_NEG, FACE_FY_POS, FACE_FY_NEG = 1, 2, 4, 8, 16
+GAIN_OUTPUTS = ("K", "Vx", "Vxx", "u_star", "faces")
+
 KKT_COLUMNS = ("cost", "stat", "prim", "comp")  # CMPC_KKT_COST .. CMPC_KKT_COMP
 
 EXPORTS = ("cmpc_params_default", "cmpc_plan_create", "cmpc_solve", "cmpc_plan_destroy",
-           "cmpc_build_dynamics", "cmpc_solve_warm", "cmpc_solve_ref", "cmpc_solve_io_run", "cmpc_kkt_run", "cmpc_generate_traj", "cmpc_leg_torque", "cmpc_srb_step",
+           "cmpc_build_dynamics", "cmpc_solve_warm", "cmpc_solve_ref", "cmpc_solve_io_run", "cmpc_kkt_run", "cmpc_gain_run", "cmpc_generate_traj", "cmpc_leg_torque", "cmpc_srb_step",
            "cmpc_plan_set_timing", "cmpc_plan_timing_read", "cmpc_plan_set_team", "cmpc_plan_team_batch",
            "cmpc_plan_set_heavy_first",
            "cmpc_plan_heavy_first_batch", "cmpc_plan_solve_kernel", "cmpc_plan_stats",
@@ -116,6 +131,9 @@ def load(path: str | Path | None = None) -> ctypes.CDLL:
     if hasattr(lib, "cmpc_kkt_run"):  # absent from builds that predate the device-side KKT check
         lib.cmpc_kkt_run.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(CKktIO), vp]
         lib.cmpc_kkt_run.restype = ctypes.c_int
+    if hasattr(lib, "cmpc_gain_run"):  # absent from builds that predate the feedback gain
+        lib.cmpc_gain_run.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(CGainIO), vp]
+        lib.cmpc_gain_run.restype = ctypes.c_int
     lib.cmpc_build_dynamics.argtypes = [vp, ctypes.c_int64, ctypes.c_float] + [vp] * 8
     lib.cmpc_build_dynamics.restype = ctypes.c_int
     if hasattr(lib, "cmpc_generate_traj"):

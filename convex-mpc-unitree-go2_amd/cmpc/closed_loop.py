@@ -53,12 +53,18 @@ class ClosedLoop:
     with recovered multipliers, the loop's ``mu`` / ``fz_min`` / ``Q`` / ``R``) into ``self.kkt``,
     a (B, 4) float64 tensor with the columns ``cmpc.KKT_COLUMNS``: a per-robot health signal
     besides ``status``.  ``self.x_solve`` holds the state the tick solved from (the plant
-    overwrites ``x``).  Both run on the tick's stream, so a captured graph carries them."""
+    overwrites ``x``).  Both run on the tick's stream, so a captured graph carries them.
+
+    ``gain=True``: every tick also evaluates the feedback gain of the returned forces
+    (``Plan.gain`` on the faces ``w`` holds) into ``self.K0``, a (B, 12, 12) float64 tensor with
+    ``K0[b] = d U[:, 0] / d x0``: between two MPC ticks ``U[:, 0] + K0 (x - x_solve)`` is the
+    first-order correction of the held forces.  It runs on the tick's stream too and keeps
+    ``self.x_solve`` as ``report`` does."""
 
     def __init__(self, B: int, plan: Optional[Plan] = None, gait_hz: float = synth.GAIT_HZ,
                  duty: float = synth.GAIT_DUTY, offsets=synth.TROT_OFFSETS, nsub: int = 20,
                  seed: int = 0, device="cuda", shift_warm: bool = True, mu=None, fz_min=None,
-                 Q=None, R=None, report: bool = False):
+                 Q=None, R=None, report: bool = False, gain: bool = False):
         self.plan = plan or Plan(SolverParams(max_batch=B))
         self.B, self.N = B, self.plan.params.N
         dev = torch.device(device)
@@ -112,9 +118,13 @@ class ClosedLoop:
             torch.as_tensor(v, dtype=f32).expand(B, 12).contiguous().to(dev, copy=True)
             for v in (Q, R))
         self.report = bool(report)
-        if self.report:
+        self.gain = bool(gain)
+        if self.report or self.gain:
             self.x_solve = torch.empty_like(self.x)
+        if self.report:
             self.kkt = torch.empty((B, 4), dtype=f64, device=dev)
+        if self.gain:
+            self.K0 = torch.empty((B, 12, 12), dtype=f64, device=dev)
         self.shift_warm = shift_warm
         self.warm = False
         self.graph = None
@@ -147,7 +157,7 @@ class ClosedLoop:
             kw = dict(w_init=self.w_init, y_init=self.y_init)
         else:
             kw = dict(w_init=self.w, y_init=self.y) if warm else {}
-        if self.report:
+        if self.report or self.gain:
             self.x_solve.copy_(self.x)
         p.solve(self.Ad, self.Bd, self.gd, self.x, self.xref, self.ct,
                 out=(self.w, self.status, self.iters), stream=stream, y_out=self.y,
@@ -155,6 +165,10 @@ class ClosedLoop:
         if self.report:
             p.kkt(self.Ad, self.Bd, self.gd, self.x_solve, self.xref, self.ct, self.w,
                   mu=self.mu, fz_min=self.fz_min, Q=self.Q, R=self.R, out=self.kkt, stream=stream)
+        if self.gain:
+            p.gain(self.Ad, self.Bd, self.gd, self.x_solve, self.xref, self.ct, w=self.w,
+                   mu=self.mu, fz_min=self.fz_min, Q=self.Q, R=self.R, out=dict(K=self.K0),
+                   stream=stream)
         sp = ctypes.c_void_p(stream.cuda_stream)
         P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
         force = self.w[:, 12 * N:]                        # U[:, 0] rows (test_MPC.py:196)

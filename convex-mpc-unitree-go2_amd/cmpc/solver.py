@@ -383,6 +383,73 @@ class Plan:
         _check(self.lib, rc, "cmpc_kkt_run")
         return out
 
+    def gain(self, Ad, Bd, gd, x0, xref, contact, w=None, faces=None, mu=None, fz_min=None,
+             Q=None, R=None, face_tol=None, want=("K",), out=None, stream=None):
+        """Feedback gain and value function of B solved instances on the device (cmpc_gain_run,
+        include/cmpc.h): on the faces its forces hold the MPC law is affine, u0 = K x0 + kappa.
+
+        ``Ad`` .. ``contact`` and ``mu`` / ``fz_min`` / ``Q`` / ``R`` as for :meth:`solve`.  The
+        held faces are read off ``w`` (B, 24N) fp32, a solve's w, by the rule of
+        :func:`cmpc.duals.recover` with ``tol = face_tol`` (None = 1e-6), or given as ``faces``
+        (B, N, 4) uint8 masks (bits ``_lib.FACE_*``; ``w`` is then ignored).  ``want`` names the
+        results, a subset of ``("K", "Vx", "Vxx", "u_star", "faces")``; ``K`` is always computed.
+        Returns a dict of device tensors: ``K`` (B, 12, 12) float64 = d u0 / d x0, ``Vx`` (B, 12)
+        and ``Vxx`` (B, 12, 12) the gradient and Hessian in x0 of the optimal cost, ``u_star``
+        (B, 12N) float64 the optimum on the held faces, ``faces`` (B, N, 4) uint8 the masks used.
+        An instance with an inconsistent mask or an invalid mu / fz_min entry or Q / R row gets
+        NaN (0xFF in ``faces``).  ``out`` is a dict of preallocated tensors for some or all of
+        the wanted names.  Asynchronous on ``stream`` (default: torch's current stream), no
+        allocation when every wanted name is in ``out``, graph-capturable; the inputs are not
+        modified and B is not limited by max_batch."""
+        if not hasattr(self.lib, "cmpc_gain_run"):
+            raise CmpcError("cmpc: this libcmpc.so has no cmpc_gain_run: Plan.gain needs a library "
+                            "built from sources that declare it")
+        want = tuple(want)
+        unknown = [n for n in want if n not in _lib.GAIN_OUTPUTS]
+        if unknown:
+            raise ValueError(f"gain: unknown result {unknown}; choose from {_lib.GAIN_OUTPUTS}")
+        if w is None and faces is None:
+            raise ValueError("gain needs w or faces: one must name the held faces")
+        N = self.params.N
+        B = Ad.shape[0]
+        if B < 1:
+            raise ValueError("gain needs at least one instance")
+        f32, f64, u8 = torch.float32, torch.float64, torch.uint8
+        io = _lib.CGainIO()
+        io.size = ctypes.sizeof(_lib.CGainIO)
+        req = dict(Ad=(Ad, f32, (B, 12, 12)), Bd=(Bd, f32, (B, N, 12, 12)), gd=(gd, f32, (B, 12)),
+                   x0=(x0, f32, (B, 12)), xref=(xref, f32, (B, N, 12)),
+                   contact=(contact, u8, (B, 4, N)))
+        opt = dict(w=(w, f32, (B, 24 * N)), faces=(faces, u8, (B, N, 4)), mu=(mu, f32, (B,)),
+                   fz_min=(fz_min, f32, (B,)), Q=(Q, f32, (B, 12)), R=(R, f32, (B, 12)))
+        for name, (t, dtype, shape) in {**req, **opt}.items():
+            if t is None and name in opt:
+                continue
+            _dev_tensor(t, name, dtype, shape)
+            self._same_device(t)
+            setattr(io, name, t.data_ptr())
+        spec = dict(K=("K", f64, (B, 12, 12)), Vx=("Vx", f64, (B, 12)), Vxx=("Vxx", f64, (B, 12, 12)),
+                    u_star=("u_star", f64, (B, 12 * N)), faces=("faces_out", u8, (B, N, 4)))
+        out = dict(out or {})
+        res = {}
+        for name in ("K",) + tuple(n for n in want if n != "K"):
+            field, dtype, shape = spec[name]
+            t = out.get(name)
+            if t is None:
+                t = torch.empty(shape, dtype=dtype, device=Ad.device)
+            _dev_tensor(t, name, dtype, shape)
+            self._same_device(t)
+            setattr(io, field, t.data_ptr())
+            res[name] = t
+        io.face_tol = 0.0 if face_tol is None else float(face_tol)
+        if stream is None:
+            stream = torch.cuda.current_stream(Ad.device)
+        sp = ctypes.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else stream)
+        with torch.cuda.device(Ad.device):
+            rc = self.lib.cmpc_gain_run(self._h, ctypes.c_int64(B), ctypes.byref(io), sp)
+        _check(self.lib, rc, "cmpc_gain_run")
+        return res
+
     def build_dynamics(self, mass, inertia, r_feet, xref, dt, out=None, stream=None):
         """Discrete dynamics (Ad, Bd, gd) of B robots on the device -- the reference's
         ComTraj._continuousDynamics + _discreteDynamics (com_trajectory.py:221-286) in closed

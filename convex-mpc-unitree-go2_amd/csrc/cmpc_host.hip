@@ -20,6 +20,7 @@
 #include "cmpc_leg.hip"       // leg controller (stance torque mapping, swing) kernel
 #include "cmpc_sim.hip"       // single-rigid-body plant (closed-loop stand-in for MuJoCo)
 #include "cmpc_kkt.hip"       // cost and KKT residuals of a batch of points
+#include "cmpc_gain.hip"      // feedback gain and value function on the held faces
 
 constexpr int kNumGroups = 3;  // solve kernels (register classes), see solve_group_kernel
 static_assert(kNumGroups == CMPC_NUM_SOLVE_KERNELS, "one timing slot per solve kernel");
@@ -421,6 +422,53 @@ int cmpc_kkt_run(cmpc_plan* pl, int64_t B, const cmpc_kkt_io* io, void* stream) 
                      k, B);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "kkt_kernel launch");
+  return CMPC_OK;
+}
+
+int cmpc_gain_run(cmpc_plan* pl, int64_t B, const cmpc_gain_io* io, void* stream) {
+  // (the struct is checked before the plan is touched)
+  if (!io) return fail(CMPC_E_INVALID, "cmpc_gain_run: null io");
+  if (io->size < offsetof(cmpc_gain_io, K) + sizeof(io->K))
+    return fail(CMPC_E_INVALID, "cmpc_gain_run: io->size is not a cmpc_gain_io size");
+  // fields past the caller's size are NULL or 0 (the struct grows at its end)
+  cmpc_gain_io a;
+  memset(&a, 0, sizeof(a));
+  memcpy(&a, io, std::min((size_t)io->size, sizeof(a)));
+  if (!pl) return fail(CMPC_E_INVALID, "cmpc_gain_run: null plan");
+  if (B < 1) return fail(CMPC_E_INVALID, "cmpc_gain_run: B must be >= 1");
+  if (!a.Ad || !a.Bd || !a.gd || !a.x0 || !a.xref || !a.contact || !a.K)
+    return fail(CMPC_E_INVALID, "cmpc_gain_run: null array argument");
+  if (!a.w && !a.faces)
+    return fail(CMPC_E_INVALID, "cmpc_gain_run: w and faces are both null (one must name the "
+                                "held faces)");
+  if (!(a.face_tol >= 0.f) || !std::isfinite(a.face_tol))
+    return fail(CMPC_E_INVALID, "cmpc_gain_run: face_tol must be finite and >= 0");
+  if (int rc = check_device(pl, "cmpc_gain_run")) return rc;
+  cmpc::GainArgs k;
+  k.N = pl->kp.N;
+  for (int i = 0; i < 12; ++i) {
+    k.Q2[i] = pl->kp.Q2[i];
+    k.R2[i] = pl->kp.R2[i];
+  }
+  k.mu = pl->kp.mu;
+  k.fz_min = pl->kp.fz_min;
+  k.tol = a.face_tol > 0.f ? (double)a.face_tol : 1e-6;
+  k.Ad = a.Ad; k.Bd = a.Bd; k.gd = a.gd; k.x0 = a.x0; k.xref = a.xref;
+  k.contact = a.contact;
+  k.mu_b = a.mu; k.fz_b = a.fz_min; k.Q = a.Q; k.R = a.R;
+  k.w = a.faces ? nullptr : a.w;
+  k.faces = a.faces;
+  k.K = a.K; k.Vx = a.Vx; k.Vxx = a.Vxx; k.u_star = a.u_star;
+  k.faces_out = a.faces_out;
+  // the forward pass needs every step's (K_k, kappa_k) in LDS; K alone keeps one slot
+  const int keep = a.u_star ? 1 : 0;
+  const size_t dyn = (size_t)(keep ? k.N : 1) * cmpc::kGainSlot * sizeof(double);
+  const long long cap = 8192;
+  const long long blocks = B < cap ? B : cap;  // grid-stride, one wave per instance
+  hipLaunchKernelGGL(cmpc::gain_kernel, dim3((unsigned)blocks), dim3(64), dyn,
+                     (hipStream_t)stream, k, B, keep);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "gain_kernel launch");
   return CMPC_OK;
 }
 

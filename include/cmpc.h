@@ -276,6 +276,63 @@ typedef struct cmpc_kkt_io {
 #define CMPC_KKT_COMP 3
 int cmpc_kkt_run(cmpc_plan* plan, int64_t B, const cmpc_kkt_io* io, void* stream);
 
+/* Feedback gain and value function of B solved instances, on the device: how the forces move
+ * when the state moves.  At its optimum the QP is an equality-constrained LQ problem on the
+ * faces of the friction pyramid its forces hold, so the MPC law is locally affine,
+ * u_0 = K x_0 + kappa.  For every instance the entry fixes a set of held faces, solves
+ *   min sum_k (x_{k+1}-xref_k)' Q (x_{k+1}-xref_k) + u_k' R u_k,  x_{k+1} = Ad x_k + Bd_k u_k + gd
+ * over the forces that stay on those faces, exactly, by the backward Riccati recursion in fp64
+ * on the fp32 inputs widened exactly, and returns
+ *   K       [B][12][12]  fp64  K[b][i][j] = d u_0[i] / d x_0[j]   (required)
+ *   Vx      [B][12]      fp64  nullable; the gradient in x_0 of the optimal cost 1/2 w'Hw + g'w
+ *   Vxx     [B][12][12]  fp64  nullable; its Hessian (symmetric)
+ *   u_star  [B][12N]     fp64  nullable; the optimum on the held faces, u_0 .. u_{N-1}
+ *   faces_out [B][N][4]  uint8 nullable; the face masks used, [step][leg]
+ * Face mask of a stance (step, leg):  bit 0  fz = fz_min;  bit 1  fx = +mu fz;  bit 2  fx = -mu fz;
+ * bit 3  fy = +mu fz;  bit 4  fy = -mu fz  (bits 5..7 are ignored).  A swing leg has f = 0
+ * whatever its mask, and faces_out holds 0 for it.  Both signs of one axis held mean fz = 0 and
+ * that axis zero; a mask is inconsistent only when both signs of an axis are set together with
+ * bit 0 and fz_min != 0.
+ *   faces   [B][N][4]  uint8  nullable; the held faces given by the caller (w is then ignored)
+ *   w       [B][24N]   fp32   nullable; with faces == NULL the masks are read off w's forces by
+ *                             the rule of cmpc_kkt_run's recovery: a force is on a face within
+ *                             face_tol x max(1, |fz|), the + face of an axis tested before the -
+ *                             face.  w and faces both NULL: CMPC_E_INVALID.
+ *   face_tol                  used when faces == NULL; 0 selects 1e-6.  Negative or not finite:
+ *                             CMPC_E_INVALID.
+ *   mu, fz_min, Q, R          nullable per-instance values, as in cmpc_kkt_io.
+ * An instance with an inconsistent mask, or with a mu / fz_min entry or Q / R row that is
+ * invalid by the rules of cmpc_solve_io, gets NaN in every fp64 output and 0xFF in faces_out; it
+ * never fails the call and the other instances are unaffected.  A step without a free force
+ * parameter contributes a zero gain.
+ * `size` is the caller's sizeof of the struct (fields past it read as NULL or 0); it must reach
+ * past `K`.  B >= 1; no workspace is used, so the plan's max_batch does not limit B.  Each sum
+ * runs in a fixed order: the results are bitwise repeatable and do not depend on B or on the
+ * instance's place in the batch.  Same guarantees as cmpc_solve: asynchronous on `stream`, no
+ * allocation, no host synchronisation, graph-capturable; the plan's device must be current. */
+typedef struct cmpc_gain_io {
+  uint32_t size;            /* sizeof of this struct in the caller's header */
+  const float *Ad, *Bd, *gd, *x0, *xref;  /* as cmpc_solve */
+  const uint8_t* contact;
+  const float *mu, *fz_min; /* [B] nullable: the plan's constants */
+  const float *Q, *R;       /* [B][12] nullable */
+  const float* w;           /* [B][24N] nullable: the point whose held faces define the law */
+  const uint8_t* faces;     /* [B][N][4] nullable: held faces given by the caller */
+  float face_tol;           /* used when faces == NULL; 0 selects 1e-6 */
+  double* K;                /* [B][12][12] out, required */
+  double* Vx;               /* [B][12] nullable */
+  double* Vxx;              /* [B][12][12] nullable */
+  double* u_star;           /* [B][12N] nullable */
+  uint8_t* faces_out;       /* [B][N][4] nullable */
+} cmpc_gain_io;
+
+#define CMPC_FACE_FZ_MIN 1
+#define CMPC_FACE_FX_POS 2
+#define CMPC_FACE_FX_NEG 4
+#define CMPC_FACE_FY_POS 8
+#define CMPC_FACE_FY_NEG 16
+int cmpc_gain_run(cmpc_plan* plan, int64_t B, const cmpc_gain_io* io, void* stream);
+
 void cmpc_plan_destroy(cmpc_plan* plan);
 
 /* QP data on the device: the reference's discrete dynamics
