@@ -46,33 +46,31 @@ class CParams(ctypes.Structure):
     ]
 
 
+def _io_fields(*names):
+    """``size``, the arrays and values every io struct opens with, then the named fields."""
+    head = ("Ad", "Bd", "gd", "x0", "xref", "contact", "mu", "fz_min")
+    return ([("size", ctypes.c_uint32)] +
+            [(n, ctypes.c_float if n == "face_tol" else ctypes.c_void_p) for n in head + names])
+
+
 class CSolveIO(ctypes.Structure):
     """cmpc_solve_io (include/cmpc.h): every argument of a solve, per-instance mu / fz_min and
     cost weights Q / R included.  ``size`` is this mirror's sizeof."""
-    _fields_ = ([("size", ctypes.c_uint32)] +
-                [(n, ctypes.c_void_p) for n in
-                 ("Ad", "Bd", "gd", "x0", "xref", "contact", "mu", "fz_min", "w_init", "y_init",
-                  "lam_init", "w_out", "y_out", "lam_out", "status", "iters", "Q", "R")])
+    _fields_ = _io_fields("w_init", "y_init", "lam_init", "w_out", "y_out", "lam_out", "status",
+                          "iters", "Q", "R")
 
 
 class CKktIO(ctypes.Structure):
     """cmpc_kkt_io (include/cmpc.h): a batch of points to evaluate, with the per-instance values
     of CSolveIO.  ``size`` is this mirror's sizeof."""
-    _fields_ = ([("size", ctypes.c_uint32)] +
-                [(n, ctypes.c_void_p) for n in
-                 ("Ad", "Bd", "gd", "x0", "xref", "contact", "mu", "fz_min", "Q", "R", "w", "lam")] +
-                [("face_tol", ctypes.c_float), ("res", ctypes.c_void_p)])
+    _fields_ = _io_fields("Q", "R", "w", "lam", "face_tol", "res")
 
 
 class CGainIO(ctypes.Structure):
     """cmpc_gain_io (include/cmpc.h): a batch whose feedback gain and value function are wanted,
     with the per-instance values of CSolveIO.  ``size`` is this mirror's sizeof."""
-    _fields_ = ([("size", ctypes.c_uint32)] +
-                [(n, ctypes.c_void_p) for n in
-                 ("Ad", "Bd", "gd", "x0", "xref", "contact", "mu", "fz_min", "Q", "R", "w",
-                  "faces")] +
-                [("face_tol", ctypes.c_float)] +
-                [(n, ctypes.c_void_p) for n in ("K", "Vx", "Vxx", "u_star", "faces_out")])
+    _fields_ = _io_fields("Q", "R", "w", "faces", "face_tol", "K", "Vx", "Vxx", "u_star",
+                          "faces_out")
 
 
 # cmpc_gain_io's face-mask bits of a stance (step, leg): CMPC_FACE_*

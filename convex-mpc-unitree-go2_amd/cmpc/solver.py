@@ -80,6 +80,28 @@ def _dev_tensor(t: torch.Tensor, name: str, dtype, shape) -> torch.Tensor:
     return t
 
 
+def _stream_ptr(stream, device) -> ctypes.c_void_p:
+    """``stream`` (None: torch's current stream on ``device``) as the C-ABI's ``void*``."""
+    if stream is None:
+        stream = torch.cuda.current_stream(device)
+    return ctypes.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else stream)
+
+
+def _problem_spec(B, N, Ad, Bd, gd, x0, xref, contact) -> dict:
+    """name -> (tensor, dtype, shape) of the six arrays of a batch of B problems."""
+    f32 = torch.float32
+    return dict(Ad=(Ad, f32, (B, 12, 12)), Bd=(Bd, f32, (B, N, 12, 12)), gd=(gd, f32, (B, 12)),
+                x0=(x0, f32, (B, 12)), xref=(xref, f32, (B, N, 12)),
+                contact=(contact, torch.uint8, (B, 4, N)))
+
+
+def _instance_spec(B, mu, fz_min, Q, R) -> dict:
+    """The same of the optional per-instance values."""
+    f32 = torch.float32
+    return dict(mu=(mu, f32, (B,)), fz_min=(fz_min, f32, (B,)), Q=(Q, f32, (B, 12)),
+                R=(R, f32, (B, 12)))
+
+
 class Plan:
     """Owns a cmpc_plan (device workspace for up to params.max_batch instances)."""
 
@@ -124,6 +146,17 @@ class Plan:
         if t.device != self.device:
             raise ValueError(f"cmpc: tensors are on {t.device} but the plan was created on "
                              f"{self.device}")
+
+    def _fill_io(self, io, required: dict, optional: dict):
+        """Check the name -> (tensor, dtype, shape) specs, in their order, and point io's fields
+        of those names at the tensors; an optional tensor that is None is skipped (NULL)."""
+        for spec, skip_none in ((required, False), (optional, True)):
+            for name, (t, dtype, shape) in spec.items():
+                if t is None and skip_none:
+                    continue
+                _dev_tensor(t, name, dtype, shape)
+                self._same_device(t)
+                setattr(io, name, t.data_ptr())
 
     def set_timing(self, enable: bool):
         _check(self.lib, self.lib.cmpc_plan_set_timing(self._h, int(bool(enable))),
@@ -222,12 +255,8 @@ class Plan:
         N = self.params.N
         B = Ad.shape[0]
         f32 = torch.float32
-        _dev_tensor(Ad, "Ad", f32, (B, 12, 12))
-        _dev_tensor(Bd, "Bd", f32, (B, N, 12, 12))
-        _dev_tensor(gd, "gd", f32, (B, 12))
-        _dev_tensor(x0, "x0", f32, (B, 12))
-        _dev_tensor(xref, "xref", f32, (B, N, 12))
-        _dev_tensor(contact, "contact", torch.uint8, (B, 4, N))
+        for name, spec in _problem_spec(B, N, Ad, Bd, gd, x0, xref, contact).items():
+            _dev_tensor(spec[0], name, *spec[1:])
         self._same_device(Ad)
         for t in (Bd, gd, x0, xref, contact):
             if t.device != Ad.device:
@@ -241,9 +270,7 @@ class Plan:
             _dev_tensor(w, "w", f32, (B, 24 * N))
             _dev_tensor(status, "status", torch.int32, (B,))
             _dev_tensor(iters, "iters", torch.int32, (B,))
-        if stream is None:
-            stream = torch.cuda.current_stream(Ad.device)
-        sp = ctypes.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else stream)
+        sp = _stream_ptr(stream, Ad.device)
         if mu is not None or fz_min is not None or Q is not None or R is not None:
             return self._solve_io(B, (Ad, Bd, gd, x0, xref, contact), (w, status, iters), sp,
                                   w_init, y_init, y_out, lam_init, lam_out, mu, fz_min, Q, R)
@@ -313,19 +340,13 @@ class Plan:
             y_out = torch.empty((B, 12 * N), dtype=f32, device=dev)
         if ret_l:
             lam_out = torch.empty((B, 52 * N), dtype=f32, device=dev)
-        opt = dict(mu=(mu, (B,)), fz_min=(fz_min, (B,)), Q=(Q, (B, 12)), R=(R, (B, 12)),
-                   w_init=(w_init, (B, 24 * N)),
-                   y_init=(y_init, (B, 12 * N)), lam_init=(lam_init, (B, 52 * N)),
-                   y_out=(y_out, (B, 12 * N)), lam_out=(lam_out, (B, 52 * N)))
         io = _lib.CSolveIO()
         io.size = ctypes.sizeof(_lib.CSolveIO)
-        for name, (t, shape) in opt.items():
-            if t is not None:
-                _dev_tensor(t, name, f32, shape)
-                self._same_device(t)
-                setattr(io, name, t.data_ptr())
-        for name, t in zip(("Ad", "Bd", "gd", "x0", "xref", "contact"), inputs):
-            setattr(io, name, t.data_ptr())
+        self._fill_io(io, _problem_spec(B, N, *inputs),
+                      dict(_instance_spec(B, mu, fz_min, Q, R),
+                           w_init=(w_init, f32, (B, 24 * N)), y_init=(y_init, f32, (B, 12 * N)),
+                           lam_init=(lam_init, f32, (B, 52 * N)), y_out=(y_out, f32, (B, 12 * N)),
+                           lam_out=(lam_out, f32, (B, 52 * N))))
         for name, t in zip(("w_out", "status", "iters"), outs):
             setattr(io, name, t.data_ptr())
         with torch.cuda.device(dev):
@@ -358,26 +379,16 @@ class Plan:
         f32 = torch.float32
         io = _lib.CKktIO()
         io.size = ctypes.sizeof(_lib.CKktIO)
-        req = dict(Ad=(Ad, f32, (B, 12, 12)), Bd=(Bd, f32, (B, N, 12, 12)), gd=(gd, f32, (B, 12)),
-                   x0=(x0, f32, (B, 12)), xref=(xref, f32, (B, N, 12)),
-                   contact=(contact, torch.uint8, (B, 4, N)), w=(w, f32, (B, 24 * N)))
-        opt = dict(lam=(lam, f32, (B, 52 * N)), mu=(mu, f32, (B,)), fz_min=(fz_min, f32, (B,)),
-                   Q=(Q, f32, (B, 12)), R=(R, f32, (B, 12)))
-        for name, (t, dtype, shape) in {**req, **opt}.items():
-            if t is None and name in opt:
-                continue
-            _dev_tensor(t, name, dtype, shape)
-            self._same_device(t)
-            setattr(io, name, t.data_ptr())
+        self._fill_io(io, dict(_problem_spec(B, N, Ad, Bd, gd, x0, xref, contact),
+                               w=(w, f32, (B, 24 * N))),
+                      dict(lam=(lam, f32, (B, 52 * N)), **_instance_spec(B, mu, fz_min, Q, R)))
         if out is None:
             out = torch.empty((B, 4), dtype=torch.float64, device=Ad.device)
         _dev_tensor(out, "out", torch.float64, (B, 4))
         self._same_device(out)
         io.res = out.data_ptr()
         io.face_tol = 0.0 if face_tol is None else float(face_tol)
-        if stream is None:
-            stream = torch.cuda.current_stream(Ad.device)
-        sp = ctypes.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else stream)
+        sp = _stream_ptr(stream, Ad.device)
         with torch.cuda.device(Ad.device):
             rc = self.lib.cmpc_kkt_run(self._h, ctypes.c_int64(B), ctypes.byref(io), sp)
         _check(self.lib, rc, "cmpc_kkt_run")
@@ -417,17 +428,9 @@ class Plan:
         f32, f64, u8 = torch.float32, torch.float64, torch.uint8
         io = _lib.CGainIO()
         io.size = ctypes.sizeof(_lib.CGainIO)
-        req = dict(Ad=(Ad, f32, (B, 12, 12)), Bd=(Bd, f32, (B, N, 12, 12)), gd=(gd, f32, (B, 12)),
-                   x0=(x0, f32, (B, 12)), xref=(xref, f32, (B, N, 12)),
-                   contact=(contact, u8, (B, 4, N)))
-        opt = dict(w=(w, f32, (B, 24 * N)), faces=(faces, u8, (B, N, 4)), mu=(mu, f32, (B,)),
-                   fz_min=(fz_min, f32, (B,)), Q=(Q, f32, (B, 12)), R=(R, f32, (B, 12)))
-        for name, (t, dtype, shape) in {**req, **opt}.items():
-            if t is None and name in opt:
-                continue
-            _dev_tensor(t, name, dtype, shape)
-            self._same_device(t)
-            setattr(io, name, t.data_ptr())
+        self._fill_io(io, _problem_spec(B, N, Ad, Bd, gd, x0, xref, contact),
+                      dict(w=(w, f32, (B, 24 * N)), faces=(faces, u8, (B, N, 4)),
+                           **_instance_spec(B, mu, fz_min, Q, R)))
         spec = dict(K=("K", f64, (B, 12, 12)), Vx=("Vx", f64, (B, 12)), Vxx=("Vxx", f64, (B, 12, 12)),
                     u_star=("u_star", f64, (B, 12 * N)), faces=("faces_out", u8, (B, N, 4)))
         out = dict(out or {})
@@ -442,9 +445,7 @@ class Plan:
             setattr(io, field, t.data_ptr())
             res[name] = t
         io.face_tol = 0.0 if face_tol is None else float(face_tol)
-        if stream is None:
-            stream = torch.cuda.current_stream(Ad.device)
-        sp = ctypes.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else stream)
+        sp = _stream_ptr(stream, Ad.device)
         with torch.cuda.device(Ad.device):
             rc = self.lib.cmpc_gain_run(self._h, ctypes.c_int64(B), ctypes.byref(io), sp)
         _check(self.lib, rc, "cmpc_gain_run")
@@ -475,9 +476,7 @@ class Plan:
             _dev_tensor(Ad, "Ad", f32, (B, 12, 12))
             _dev_tensor(Bd, "Bd", f32, (B, N, 12, 12))
             _dev_tensor(gd, "gd", f32, (B, 12))
-        if stream is None:
-            stream = torch.cuda.current_stream(mass.device)
-        sp = ctypes.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else stream)
+        sp = _stream_ptr(stream, mass.device)
         with torch.cuda.device(mass.device):
             rc = self.lib.cmpc_build_dynamics(
                 self._h, ctypes.c_int64(B), ctypes.c_float(dt),
@@ -519,9 +518,7 @@ class Plan:
             _dev_tensor(xref, "xref", f32, (B, N, 12))
             _dev_tensor(contact, "contact", torch.uint8, (B, 4, N))
             _dev_tensor(r_feet, "r_feet", f32, (B, N, 4, 3))
-        if stream is None:
-            stream = torch.cuda.current_stream(x0.device)
-        sp = ctypes.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else stream)
+        sp = _stream_ptr(stream, x0.device)
         with torch.cuda.device(x0.device):
             rc = self.lib.cmpc_generate_traj(
                 self._h, ctypes.c_int64(B), ctypes.c_double(dt),
@@ -559,9 +556,7 @@ class Plan:
             self._same_device(x)
         tau = torch.empty((B, 12), dtype=f64, device=t.device) if out is None else out
         _dev_tensor(tau, "tau", f64, (B, 12))
-        if stream is None:
-            stream = torch.cuda.current_stream(t.device)
-        sp = ctypes.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else stream)
+        sp = _stream_ptr(stream, t.device)
         P = lambda x: ctypes.c_void_p(x.data_ptr())  # noqa: E731
         with torch.cuda.device(t.device):
             rc = self.lib.cmpc_leg_torque(

@@ -20,7 +20,7 @@
 // then K = K_0, Vxx = 2 P_0, Vx = 2 (P_0 x_0 + q_0) and the forward pass u_k = K_k x_k + kappa_k.
 //
 // One 64-lane wave per instance, fp64 on the fp32 inputs widened exactly.  The instance is
-// staged in LDS as in cmpc_kkt.hip (16-byte loads, all issued before the first is used).  The
+// staged in LDS by cmpc_problem.h (16-byte loads, all issued before the first is used).  The
 // eight 12x12 products of a step run on the f64 matrix cores (v_mfma_f64_16x16x4_f64, three per
 // product, the matrices padded to 16x16), chained from register to register: a product comes
 // out in the layout the next one takes as its B operand or as a transposed A operand, and
@@ -32,42 +32,19 @@
 // instance's place in the batch.  No atomics, no workspace.
 //
 // This file is compiled as part of cmpc_host.hip (single translation unit).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "cmpc_problem.h"
 
 namespace cmpc {
 
 struct GainArgs {
-  int N;
-  float Q2[12], R2[12];  // the plan's constants: 2Q, 2R
-  float mu, fz_min;
-  double tol;            // face tolerance (faces == NULL)
-  const float *Ad, *Bd, *gd, *x0, *xref;
-  const uint8_t* contact;
-  const float *mu_b, *fz_b, *Q, *R;  // nullable per-instance values
-  const float* w;        // nullable
+  ProblemArgs p;
+  const float* w;        // nullable: its forces' faces by face_rule with p.tol
   const uint8_t* faces;  // nullable
   double *K, *Vx, *Vxx, *u_star;  // all but K nullable
   uint8_t* faces_out;             // nullable
 };
 
 constexpr int kGainSlot = 156;  // doubles of one (K_k, kappa_k) slot in LDS
-
-// The faces a stance force holds (cmpc/duals.py recover, kkt_recover_leg): each product rounded
-// on its own, the + face of an axis tested before the - face.
-__device__ inline unsigned gain_classify(double fx, double fy, double fz, double mu, double fz_min,
-                                         double tol) {
-#pragma clang fp contract(off)
-  const double scale = tol * fmax(1.0, fabs(fz));
-  const double mf = mu * fz;
-  unsigned m = 0;
-  if (fabs(fx - mf) <= scale) m |= 2u;
-  else if (fabs(fx + mf) <= scale) m |= 4u;
-  if (fabs(fy - mf) <= scale) m |= 8u;
-  else if (fabs(fy + mf) <= scale) m |= 16u;
-  if (fabs(fz - fz_min) <= scale) m |= 1u;
-  return m;
-}
 
 // The affine set f = Z p + c of a stance leg's mask: free[3] the slots in use, zx / zy the x / y
 // entries of slot 2's column.  false: the mask is inconsistent.
@@ -120,12 +97,8 @@ __device__ inline double gain_rcp(double x) {
 }
 
 __global__ void __launch_bounds__(64) gain_kernel(GainArgs a, int64_t B, int keep_steps) {
-  __shared__ __attribute__((aligned(16))) float sBd[16 * 144];
-  __shared__ __attribute__((aligned(16))) float sAd[144];
-  __shared__ __attribute__((aligned(16))) float sXr[12 * 16];
-  __shared__ __attribute__((aligned(16))) float sGX[24];       // gd, x0
-  __shared__ uint8_t sC[64];                                   // contact [4][N]
-  __shared__ double sQ[12], sR[12];
+  __shared__ ProblemLds sp;
+  auto& [sBd, sAd, sXr, sGX, sQ, sR, sC] = sp;
   __shared__ float sZx[64], sZy[64];                           // per (step, leg): +-mu or 0, exact
   __shared__ double sCv[12 * 16], sD[12 * 16];                 // c_k and diag(Z'RZ) per step
   __shared__ double sDv[12 * 16];                              // d_k = Bd_k c_k + gd per step
@@ -139,52 +112,22 @@ __global__ void __launch_bounds__(64) gain_kernel(GainArgs a, int64_t B, int kee
   double* const su = sY + 12;
   extern __shared__ double sK[];  // keep_steps ? N : 1 slots of (K_k [12][12], kappa_k [12])
   const int lane = threadIdx.x;
-  const int N = a.N;
+  const int N = a.p.N;
 
   for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
-    const int e12 = min(lane, 11);
-    float q2 = 0.f, r2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 12; ++i)
-      if (e12 == i) { q2 = a.Q2[i]; r2 = a.R2[i]; }
-    // (an absent array reads a word that is there and drops it: a load under a branch would be
-    // waited for at the branch's end)
-    const float* const dummy = a.gd + b * 12;
-    const float mu_l = *(a.mu_b ? a.mu_b + b : dummy), fz_l = *(a.fz_b ? a.fz_b + b : dummy);
-    const float q_l = (a.Q ? a.Q + b * 12 : dummy)[e12], r_l = (a.R ? a.R + b * 12 : dummy)[e12];
-
-    // ---- stage the instance: every load is issued before the first LDS write waits for it
-    // (indices clamped into the instance instead of predicated, as in kkt_kernel)
-    uint8_t fgiven;
-    {
-      const float4* gB = reinterpret_cast<const float4*>(a.Bd + b * N * 144);
-      const float4* gU = a.w ? reinterpret_cast<const float4*>(a.w + b * N * 24 + 12 * N)
-                             : reinterpret_cast<const float4*>(a.xref + b * N * 12);
-      float4 vB[9];
-      int eB[9];
-#pragma unroll
-      for (int t = 0; t < 9; ++t) vB[t] = gB[eB[t] = min(lane + 64 * t, 36 * N - 1)];
-      const int eA = min(lane, 35), eX = min(lane, 3 * N - 1), eG = min(lane, 5),
-                eC = min(lane, 4 * N - 1);
-      const float4 vU = gU[eX];
-      const float4 vA = reinterpret_cast<const float4*>(a.Ad + b * 144)[eA];
-      const float4 vX = reinterpret_cast<const float4*>(a.xref + b * N * 12)[eX];
-      const float4 vG = eG < 3 ? reinterpret_cast<const float4*>(a.gd + b * 12)[eG]
-                               : reinterpret_cast<const float4*>(a.x0 + b * 12)[eG - 3];
-      const uint8_t c = a.contact[b * N * 4 + eC];
-      fgiven = (a.faces ? a.faces : a.contact)[b * N * 4 + eC];
-#pragma unroll
-      for (int t = 0; t < 9; ++t) reinterpret_cast<float4*>(sBd)[eB[t]] = vB[t];
-      reinterpret_cast<float4*>(sU)[eX] = vU;
-      reinterpret_cast<float4*>(sAd)[eA] = vA;
-      reinterpret_cast<float4*>(sXr)[eX] = vX;
-      reinterpret_cast<float4*>(sGX)[eG] = vG;
-      sC[eC] = c;
-    }
-    const double mu = (double)(a.mu_b ? mu_l : a.mu), fz_min = (double)(a.fz_b ? fz_l : a.fz_min);
-    const double q = a.Q ? (double)q_l : 0.5 * (double)q2, r = a.R ? (double)r_l : 0.5 * (double)r2;
-    sQ[e12] = q;
-    sR[e12] = r;
+    // ---- stage the instance: the problem's loads, then the given faces and the forces (xref
+    // where w is absent: read and dropped), all issued before the first LDS write waits for one.
+    // The faces go before the forces: they are used under a branch only, and the forces' LDS
+    // write, waiting for the last load, covers them.  Pending into the next instance they make
+    // the first write of their register wait for everything issued before it.
+    const ProblemLoads ld = problem_issue(a.p, b, lane);
+    const uint8_t fgiven = (a.faces ? a.faces : a.p.contact)[b * N * 4 + ld.eC];
+    const float4 vU = (a.w ? reinterpret_cast<const float4*>(a.w + b * N * 24 + 12 * N)
+                           : reinterpret_cast<const float4*>(a.p.xref + b * N * 12))[ld.eX];
+    problem_commit(sp, ld);
+    reinterpret_cast<float4*>(sU)[ld.eX] = vU;
+    const ProblemConsts pc = problem_consts(a.p, sp, ld);
+    const double mu = pc.mu, fz_min = pc.fz_min;
     __syncthreads();
 
     // ---- one lane per (step, leg): the mask, then its affine set
@@ -195,8 +138,8 @@ __global__ void __launch_bounds__(64) gain_kernel(GainArgs a, int64_t B, int kee
       const bool stance = sC[leg * N + k] != 0;
       if (stance)
         mask = a.faces ? (fgiven & 31u)
-                       : gain_classify((double)sU[k * 12 + 3 * leg], (double)sU[k * 12 + 3 * leg + 1],
-                                       (double)sU[k * 12 + 3 * leg + 2], mu, fz_min, a.tol);
+                       : face_rule((double)sU[k * 12 + 3 * leg], (double)sU[k * 12 + 3 * leg + 1],
+                                   (double)sU[k * 12 + 3 * leg + 2], mu, fz_min, a.p.tol);
       bool fr[3];
       double zx, zy, c[3];
       ok = gain_leg_set(mask, mu, fz_min, fr, zx, zy, c);
@@ -211,10 +154,9 @@ __global__ void __launch_bounds__(64) gain_kernel(GainArgs a, int64_t B, int kee
       sD[lane * 3 + 1] = fr[1] ? ry : 0.0;
       sD[lane * 3 + 2] = fr[2] ? fma(zx * zx, rx, fma(zy * zy, ry, rz)) : 0.0;
     }
-    // an inconsistent mask or an invalid entry (the rules of cmpc_solve_io_run): NaN in every
-    // output, 0xFF in faces_out; the same decision in every lane
-    if (__any(!ok) || __any(!(q >= 0.0 && isfinite(q) && r > 0.0 && isfinite(r))) ||
-        !(mu > 0.0 && isfinite(mu) && isfinite(fz_min))) {
+    // an inconsistent mask or an invalid entry: NaN in every output, 0xFF in faces_out; the same
+    // decision in every lane
+    if (__any(!ok) || !pc.valid) {
       const double nan = __builtin_nan("");
       for (int e = lane; e < 144; e += 64) {
         a.K[b * 144 + e] = nan;

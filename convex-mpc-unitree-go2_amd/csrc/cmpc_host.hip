@@ -119,6 +119,59 @@ bool has_group(const cmpc_plan* pl, int k) {
   return k == 0 || cmpc::kBinCap[k == 1 ? 1 : 3] < 12 * pl->kp.N;
 }
 
+// The zero-extended copy of a caller's io struct: fields past the caller's size are NULL or 0
+// (the structs grow at their end); a size below min_size is not one of the struct's sizes.
+// Checked before the plan is touched.
+template <class IO>
+int io_copy(const IO* io, size_t min_size, const char* what, const char* type, IO& a) {
+  if (!io) return fail(CMPC_E_INVALID, std::string(what) + ": null io");
+  if (io->size < min_size)
+    return fail(CMPC_E_INVALID, std::string(what) + ": io->size is not a " + type + " size");
+  memset(&a, 0, sizeof(a));
+  memcpy(&a, io, std::min((size_t)io->size, sizeof(a)));
+  return CMPC_OK;
+}
+
+// The checks of an evaluation entry (cmpc_kkt_io, cmpc_gain_io) after io_copy: plan, B, the six
+// problem arrays, face_tol, the device.  `own`: the entry's own required arrays are there;
+// `between`: the message of a failed check of the entry's own that ranks after the arrays, or NULL.
+template <class IO>
+int check_problem(const cmpc_plan* pl, int64_t B, const IO& a, bool own, const char* what,
+                  const char* between = nullptr) {
+  const std::string w(what);
+  if (!pl) return fail(CMPC_E_INVALID, w + ": null plan");
+  if (B < 1) return fail(CMPC_E_INVALID, w + ": B must be >= 1");
+  if (!a.Ad || !a.Bd || !a.gd || !a.x0 || !a.xref || !a.contact || !own)
+    return fail(CMPC_E_INVALID, w + ": null array argument");
+  if (between) return fail(CMPC_E_INVALID, w + between);
+  if (!(a.face_tol >= 0.f) || !std::isfinite(a.face_tol))
+    return fail(CMPC_E_INVALID, w + ": face_tol must be finite and >= 0");
+  return check_device(pl, what);
+}
+
+// the kernels' common argument block from the plan's constants and the io fields
+template <class IO>
+cmpc::ProblemArgs problem_args(const cmpc_plan* pl, const IO& a) {
+  cmpc::ProblemArgs k;
+  k.N = pl->kp.N;
+  for (int i = 0; i < 12; ++i) {
+    k.Q2[i] = pl->kp.Q2[i];
+    k.R2[i] = pl->kp.R2[i];
+  }
+  k.mu = pl->kp.mu;
+  k.fz_min = pl->kp.fz_min;
+  k.tol = a.face_tol > 0.f ? (double)a.face_tol : 1e-6;
+  k.Ad = a.Ad; k.Bd = a.Bd; k.gd = a.gd; k.x0 = a.x0; k.xref = a.xref;
+  k.contact = a.contact;
+  k.mu_b = a.mu; k.fz_b = a.fz_min; k.Q = a.Q; k.R = a.R;
+  return k;
+}
+
+// blocks of a grid-stride launch over B items
+unsigned grid_stride_blocks(int64_t B, int64_t cap = 8192) {
+  return (unsigned)std::min(B, cap);
+}
+
 }  // namespace
 
 extern "C" {
@@ -360,14 +413,9 @@ int cmpc_solve_ref(cmpc_plan* pl, int64_t B, const float* Ad, const float* Bd, c
 }
 
 int cmpc_solve_io_run(cmpc_plan* pl, int64_t B, const cmpc_solve_io* io, void* stream) {
-  // (the struct is checked before the plan is touched)
-  if (!io) return fail(CMPC_E_INVALID, "cmpc_solve_io_run: null io");
-  // fields past the caller's size are NULL (the struct grows at its end)
   cmpc_solve_io a;
-  memset(&a, 0, sizeof(a));
-  if (io->size < offsetof(cmpc_solve_io, Ad))
-    return fail(CMPC_E_INVALID, "cmpc_solve_io_run: io->size is not a cmpc_solve_io size");
-  memcpy(&a, io, std::min((size_t)io->size, sizeof(a)));
+  if (int rc = io_copy(io, offsetof(cmpc_solve_io, Ad), "cmpc_solve_io_run", "cmpc_solve_io", a))
+    return rc;
   if ((a.y_init || a.y_out) && (a.lam_init || a.lam_out))
     return fail(CMPC_E_INVALID, "cmpc_solve_io_run: y_init / y_out (this solver's dual) and "
                                 "lam_init / lam_out (the reference's multipliers) are exclusive");
@@ -386,87 +434,35 @@ int cmpc_solve_io_run(cmpc_plan* pl, int64_t B, const cmpc_solve_io* io, void* s
 }
 
 int cmpc_kkt_run(cmpc_plan* pl, int64_t B, const cmpc_kkt_io* io, void* stream) {
-  // (the struct is checked before the plan is touched)
-  if (!io) return fail(CMPC_E_INVALID, "cmpc_kkt_run: null io");
-  if (io->size < offsetof(cmpc_kkt_io, res) + sizeof(io->res))
-    return fail(CMPC_E_INVALID, "cmpc_kkt_run: io->size is not a cmpc_kkt_io size");
-  // fields past the caller's size are NULL or 0 (the struct grows at its end)
   cmpc_kkt_io a;
-  memset(&a, 0, sizeof(a));
-  memcpy(&a, io, std::min((size_t)io->size, sizeof(a)));
-  if (!pl) return fail(CMPC_E_INVALID, "cmpc_kkt_run: null plan");
-  if (B < 1) return fail(CMPC_E_INVALID, "cmpc_kkt_run: B must be >= 1");
-  if (!a.Ad || !a.Bd || !a.gd || !a.x0 || !a.xref || !a.contact || !a.w || !a.res)
-    return fail(CMPC_E_INVALID, "cmpc_kkt_run: null array argument");
-  if (!(a.face_tol >= 0.f) || !std::isfinite(a.face_tol))
-    return fail(CMPC_E_INVALID, "cmpc_kkt_run: face_tol must be finite and >= 0");
-  if (int rc = check_device(pl, "cmpc_kkt_run")) return rc;
-  cmpc::KktArgs k;
-  k.N = pl->kp.N;
-  for (int i = 0; i < 12; ++i) {
-    k.Q2[i] = pl->kp.Q2[i];
-    k.R2[i] = pl->kp.R2[i];
-  }
-  k.mu = pl->kp.mu;
-  k.fz_min = pl->kp.fz_min;
-  k.tol = a.face_tol > 0.f ? (double)a.face_tol : 1e-6;
-  k.Ad = a.Ad; k.Bd = a.Bd; k.gd = a.gd; k.x0 = a.x0; k.xref = a.xref;
-  k.contact = a.contact;
-  k.mu_b = a.mu; k.fz_b = a.fz_min; k.Q = a.Q; k.R = a.R;
-  k.w = a.w;
-  k.lam = a.lam;
-  k.res = a.res;
-  const long long cap = 8192;
-  const long long blocks = B < cap ? B : cap;  // grid-stride, one wave per instance
-  hipLaunchKernelGGL(cmpc::kkt_kernel, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream,
-                     k, B);
+  if (int rc = io_copy(io, offsetof(cmpc_kkt_io, res) + sizeof(io->res), "cmpc_kkt_run",
+                       "cmpc_kkt_io", a))
+    return rc;
+  if (int rc = check_problem(pl, B, a, a.w && a.res, "cmpc_kkt_run")) return rc;
+  const cmpc::KktArgs k{problem_args(pl, a), a.w, a.lam, a.res};
+  hipLaunchKernelGGL(cmpc::kkt_kernel, dim3(grid_stride_blocks(B)), dim3(64), 0,
+                     (hipStream_t)stream, k, B);  // one wave per instance
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "kkt_kernel launch");
   return CMPC_OK;
 }
 
 int cmpc_gain_run(cmpc_plan* pl, int64_t B, const cmpc_gain_io* io, void* stream) {
-  // (the struct is checked before the plan is touched)
-  if (!io) return fail(CMPC_E_INVALID, "cmpc_gain_run: null io");
-  if (io->size < offsetof(cmpc_gain_io, K) + sizeof(io->K))
-    return fail(CMPC_E_INVALID, "cmpc_gain_run: io->size is not a cmpc_gain_io size");
-  // fields past the caller's size are NULL or 0 (the struct grows at its end)
   cmpc_gain_io a;
-  memset(&a, 0, sizeof(a));
-  memcpy(&a, io, std::min((size_t)io->size, sizeof(a)));
-  if (!pl) return fail(CMPC_E_INVALID, "cmpc_gain_run: null plan");
-  if (B < 1) return fail(CMPC_E_INVALID, "cmpc_gain_run: B must be >= 1");
-  if (!a.Ad || !a.Bd || !a.gd || !a.x0 || !a.xref || !a.contact || !a.K)
-    return fail(CMPC_E_INVALID, "cmpc_gain_run: null array argument");
-  if (!a.w && !a.faces)
-    return fail(CMPC_E_INVALID, "cmpc_gain_run: w and faces are both null (one must name the "
-                                "held faces)");
-  if (!(a.face_tol >= 0.f) || !std::isfinite(a.face_tol))
-    return fail(CMPC_E_INVALID, "cmpc_gain_run: face_tol must be finite and >= 0");
-  if (int rc = check_device(pl, "cmpc_gain_run")) return rc;
-  cmpc::GainArgs k;
-  k.N = pl->kp.N;
-  for (int i = 0; i < 12; ++i) {
-    k.Q2[i] = pl->kp.Q2[i];
-    k.R2[i] = pl->kp.R2[i];
-  }
-  k.mu = pl->kp.mu;
-  k.fz_min = pl->kp.fz_min;
-  k.tol = a.face_tol > 0.f ? (double)a.face_tol : 1e-6;
-  k.Ad = a.Ad; k.Bd = a.Bd; k.gd = a.gd; k.x0 = a.x0; k.xref = a.xref;
-  k.contact = a.contact;
-  k.mu_b = a.mu; k.fz_b = a.fz_min; k.Q = a.Q; k.R = a.R;
-  k.w = a.faces ? nullptr : a.w;
-  k.faces = a.faces;
-  k.K = a.K; k.Vx = a.Vx; k.Vxx = a.Vxx; k.u_star = a.u_star;
-  k.faces_out = a.faces_out;
+  if (int rc = io_copy(io, offsetof(cmpc_gain_io, K) + sizeof(io->K), "cmpc_gain_run",
+                       "cmpc_gain_io", a))
+    return rc;
+  if (int rc = check_problem(pl, B, a, a.K, "cmpc_gain_run",
+                             a.w || a.faces ? nullptr : ": w and faces are both null (one must "
+                                                        "name the held faces)"))
+    return rc;
+  const cmpc::GainArgs k{problem_args(pl, a), a.faces ? nullptr : a.w, a.faces, a.K, a.Vx, a.Vxx,
+                         a.u_star, a.faces_out};
   // the forward pass needs every step's (K_k, kappa_k) in LDS; K alone keeps one slot
   const int keep = a.u_star ? 1 : 0;
-  const size_t dyn = (size_t)(keep ? k.N : 1) * cmpc::kGainSlot * sizeof(double);
-  const long long cap = 8192;
-  const long long blocks = B < cap ? B : cap;  // grid-stride, one wave per instance
-  hipLaunchKernelGGL(cmpc::gain_kernel, dim3((unsigned)blocks), dim3(64), dyn,
-                     (hipStream_t)stream, k, B, keep);
+  const size_t dyn = (size_t)(keep ? k.p.N : 1) * cmpc::kGainSlot * sizeof(double);
+  hipLaunchKernelGGL(cmpc::gain_kernel, dim3(grid_stride_blocks(B)), dim3(64), dyn,
+                     (hipStream_t)stream, k, B, keep);  // one wave per instance
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "gain_kernel launch");
   return CMPC_OK;
@@ -665,9 +661,8 @@ int cmpc_build_dynamics(cmpc_plan* pl, int64_t B, float dt, const float* mass,
   if (B == 0) return CMPC_OK;
   if (!mass || !inertia || !r_feet || !xref || !Ad || !Bd || !gd)
     return fail(CMPC_E_INVALID, "cmpc_build_dynamics: null array argument");
-  const long long cap = 8192;
-  const long long blocks = B < cap ? B : cap;  // grid-stride: ~32 resident waves per CU
-  hipLaunchKernelGGL(cmpc::dynamics_kernel, dim3((unsigned)blocks), dim3(64), 0,
+  // (grid-stride: ~32 resident waves per CU)
+  hipLaunchKernelGGL(cmpc::dynamics_kernel, dim3(grid_stride_blocks(B)), dim3(64), 0,
                      (hipStream_t)stream, pl->kp.N, (double)dt, B, mass, inertia, r_feet, xref, Ad,
                      Bd, gd);
   hipError_t e = hipGetLastError();
@@ -687,11 +682,9 @@ int cmpc_generate_traj(cmpc_plan* pl, int64_t B, double dt, const float* x0, dou
   if (!x0 || !pos_des || !cmd || !t_now || !gait || !foot_lever || !hip || !xref || !contact ||
       !r_feet)
     return fail(CMPC_E_INVALID, "cmpc_generate_traj: null array argument");
-  const long long cap = 8192;
   // one wave per group of cmpc::kTrajGroup robots (grid-stride over groups)
-  const long long groups = (B + cmpc::kTrajGroup - 1) / cmpc::kTrajGroup;
-  const long long blocks = groups < cap ? groups : cap;
-  hipLaunchKernelGGL(cmpc::traj_group_kernel, dim3((unsigned)blocks), dim3(64), 0,
+  const unsigned blocks = grid_stride_blocks((B + cmpc::kTrajGroup - 1) / cmpc::kTrajGroup);
+  hipLaunchKernelGGL(cmpc::traj_group_kernel, dim3(blocks), dim3(64), 0,
                      (hipStream_t)stream, pl->kp.N, dt, B, x0, pos_des, cmd, t_now, gait,
                      foot_lever, hip, xref, contact, r_feet);
   hipError_t e = hipGetLastError();
@@ -716,9 +709,9 @@ int cmpc_leg_torque(cmpc_plan* pl, int64_t B, const double* t, const double* gai
     return fail(CMPC_E_INVALID, "cmpc_leg_torque: null array argument");
   cmpc::LegArgs a{t, gait, force, force_stride, J_foot, J_full, M, C, g, dq, Jdot_dq, foot_pos,
                   foot_vel, body, hip, state, tau_max, tau};
-  const long long blocks = B < 16384 ? B : 16384;  // grid-stride, one wave per robot
-  hipLaunchKernelGGL(cmpc::leg_kernel, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream,
-                     B, a);
+  // (one wave per robot)
+  hipLaunchKernelGGL(cmpc::leg_kernel, dim3(grid_stride_blocks(B, 16384)), dim3(64), 0,
+                     (hipStream_t)stream, B, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "leg_kernel launch");
   return CMPC_OK;

@@ -16,28 +16,22 @@
 //
 // One 64-lane wave per instance, everything in fp64 on the fp32 inputs widened exactly.  The
 // wave stages the instance in LDS with coalesced 16-byte loads (all issued before the first is
-// used: ~15 KB in flight per wave), the multipliers as doubles; then every (step, row) is one
+// used: ~15 KB in flight per wave; the problem's part by cmpc_problem.h, shared with
+// cmpc_gain.hip), the multipliers as doubles; then every (step, row) is one
 // lane's sequential sum in a fixed order, and the four results are butterfly reductions over the
 // lanes: bitwise repeatable, independent of B and of the instance's place in the batch.  The
 // adjoint recursion is the only serial part (N steps of a 12-term product on 12 lanes).
 // No atomics, no workspace.
 //
 // This file is compiled as part of cmpc_host.hip (single translation unit).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "cmpc_problem.h"
 
 namespace cmpc {
 
 struct KktArgs {
-  int N;
-  float Q2[12], R2[12];  // the plan's constants: 2Q, 2R
-  float mu, fz_min;
-  double tol;            // face tolerance of the recovery (lam == NULL)
-  const float *Ad, *Bd, *gd, *x0, *xref;
-  const uint8_t* contact;
-  const float *mu_b, *fz_b, *Q, *R;  // nullable per-instance values
+  ProblemArgs p;
   const float* w;
-  const float* lam;      // nullable
+  const float* lam;      // nullable: recovered with p.tol
   double* res;
 };
 
@@ -64,8 +58,8 @@ __device__ inline double kkt_comp(double lam, double v, double lo, double hi) {
 }
 
 // The multipliers of one (step, leg) from s = 2R u - Bd' lam_eq restricted to the leg
-// (cmpc/duals.py recover).  The face tests round each product on its own, as NumPy does, so
-// that a force on a threshold is classified the same way on both sides.
+// (cmpc/duals.py recover): the faces it holds by face_rule, a multiplier per held face.  rz too
+// rounds its product on its own, as NumPy does.
 __device__ inline void kkt_recover_leg(bool stance, const double s[3], double fx, double fy,
                                        double fz, double mu, double fz_min, double tol,
                                        double lf[4], double lx[3]) {
@@ -78,73 +72,43 @@ __device__ inline void kkt_recover_leg(bool stance, const double s[3], double fx
     lx[2] = -s[2];
     return;
   }
-  const double scale = tol * fmax(1.0, fabs(fz));
-  const double mf = mu * fz;
-  if (fabs(fx - mf) <= scale) lf[0] = fmax(-s[0], 0.0);
-  else if (fabs(fx + mf) <= scale) lf[1] = fmax(s[0], 0.0);
-  if (fabs(fy - mf) <= scale) lf[2] = fmax(-s[1], 0.0);
-  else if (fabs(fy + mf) <= scale) lf[3] = fmax(s[1], 0.0);
+  const unsigned m = face_rule(fx, fy, fz, mu, fz_min, tol);
+  if (m & CMPC_FACE_FX_POS) lf[0] = fmax(-s[0], 0.0);
+  if (m & CMPC_FACE_FX_NEG) lf[1] = fmax(s[0], 0.0);
+  if (m & CMPC_FACE_FY_POS) lf[2] = fmax(-s[1], 0.0);
+  if (m & CMPC_FACE_FY_NEG) lf[3] = fmax(s[1], 0.0);
   const double rz = s[2] - mu * (((lf[0] + lf[1]) + lf[2]) + lf[3]);  // = -lam_x[fz]
-  if (fabs(fz - fz_min) <= scale) lx[2] = fmin(-rz, 0.0);  // active lower bound: lam <= 0
+  if (m & CMPC_FACE_FZ_MIN) lx[2] = fmin(-rz, 0.0);  // active lower bound: lam <= 0
 }
 
 __global__ void __launch_bounds__(64) kkt_kernel(KktArgs a, int64_t B) {
-  __shared__ __attribute__((aligned(16))) float sBd[16 * 144];
-  __shared__ __attribute__((aligned(16))) float sAd[144];
+  __shared__ ProblemLds sp;
   __shared__ __attribute__((aligned(16))) float sW[24 * 16];   // [x_1..x_N | u_0..u_{N-1}]
-  __shared__ __attribute__((aligned(16))) float sXr[12 * 16];
-  __shared__ __attribute__((aligned(16))) float sGX[24];       // gd, x0
   __shared__ __attribute__((aligned(16))) double sL[52 * 16];  // [lam_x | lam_a], lam's layout
-  __shared__ double sQ[12], sR[12];
-  __shared__ uint8_t sC[64];                                   // contact [4][N]
+  auto& [sBd, sAd, sXr, sGX, sQ, sR, sC] = sp;
   const int lane = threadIdx.x;
-  const int N = a.N;
+  const int N = a.p.N;
   double* const Lx = sL;            // lam_x: states [0, 12N), forces [12N, 24N)
   double* const Ld = sL + 24 * N;   // lam_a, dynamics rows
   double* const Lf = sL + 36 * N;   // lam_a, friction rows [(k, leg)][4]
   const float* const sU = sW + 12 * N;
 
   for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
-    // the instance's constants (lanes past 11 repeat entry 11); their loads go out with the
-    // staging loads below and are first used after them
-    const int e12 = min(lane, 11);
-    float q2 = 0.f, r2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 12; ++i)
-      if (e12 == i) { q2 = a.Q2[i]; r2 = a.R2[i]; }
-    // (an absent array reads a word of gd instead, which is dropped: a load under a branch
-    // would be waited for at the branch's end)
-    const float* const dummy = a.gd + b * 12;
-    const float mu_l = *(a.mu_b ? a.mu_b + b : dummy), fz_l = *(a.fz_b ? a.fz_b + b : dummy);
-    const float q_l = (a.Q ? a.Q + b * 12 : dummy)[e12], r_l = (a.R ? a.R + b * 12 : dummy)[e12];
-
-    // ---- stage the instance: every load is issued before the first LDS write waits for it
+    // ---- stage the instance: the problem's loads, then w's and lam's, all issued before the
+    // first LDS write waits for one (indices clamped, not predicated: problem_issue)
+    const ProblemLoads ld = problem_issue(a.p, b, lane);
     {
-      const float4* gB = reinterpret_cast<const float4*>(a.Bd + b * N * 144);
       const float4* gW = reinterpret_cast<const float4*>(a.w + b * N * 24);
       const float4* gL = a.lam ? reinterpret_cast<const float4*>(a.lam + b * N * 52) : nullptr;
-      // Load and LDS indices are clamped into the instance instead of predicated (lanes past the
-      // end repeat its last element): a predicated copy is compiled as load-wait-store per
-      // piece, which leaves one load in flight instead of all of them.
-      float4 vB[9], vW[2], vL[4];
-      int eB[9], eW[2], eL[4];
-#pragma unroll
-      for (int t = 0; t < 9; ++t) vB[t] = gB[eB[t] = min(lane + 64 * t, 36 * N - 1)];
+      float4 vW[2], vL[4];
+      int eW[2], eL[4];
 #pragma unroll
       for (int t = 0; t < 2; ++t) vW[t] = gW[eW[t] = min(lane + 64 * t, 6 * N - 1)];
       if (gL) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) vL[t] = gL[eL[t] = min(lane + 64 * t, 13 * N - 1)];
       }
-      const int eA = min(lane, 35), eX = min(lane, 3 * N - 1), eG = min(lane, 5),
-                eC = min(lane, 4 * N - 1);
-      const float4 vA = reinterpret_cast<const float4*>(a.Ad + b * 144)[eA];
-      const float4 vX = reinterpret_cast<const float4*>(a.xref + b * N * 12)[eX];
-      const float4 vG = eG < 3 ? reinterpret_cast<const float4*>(a.gd + b * 12)[eG]
-                               : reinterpret_cast<const float4*>(a.x0 + b * 12)[eG - 3];
-      const uint8_t c = a.contact[b * N * 4 + eC];
-#pragma unroll
-      for (int t = 0; t < 9; ++t) reinterpret_cast<float4*>(sBd)[eB[t]] = vB[t];
+      problem_commit(sp, ld);
 #pragma unroll
       for (int t = 0; t < 2; ++t) reinterpret_cast<float4*>(sW)[eW[t]] = vW[t];
       if (gL) {
@@ -154,20 +118,12 @@ __global__ void __launch_bounds__(64) kkt_kernel(KktArgs a, int64_t B) {
           reinterpret_cast<double2*>(sL)[2 * eL[t] + 1] = make_double2((double)vL[t].z, (double)vL[t].w);
         }
       }
-      reinterpret_cast<float4*>(sAd)[eA] = vA;
-      reinterpret_cast<float4*>(sXr)[eX] = vX;
-      reinterpret_cast<float4*>(sGX)[eG] = vG;
-      sC[eC] = c;
     }
-    const double mu = (double)(a.mu_b ? mu_l : a.mu), fz_min = (double)(a.fz_b ? fz_l : a.fz_min);
-    const double q = a.Q ? (double)q_l : 0.5 * (double)q2, r = a.R ? (double)r_l : 0.5 * (double)r2;
-    sQ[e12] = q;
-    sR[e12] = r;
+    const ProblemConsts pc = problem_consts(a.p, sp, ld);
+    const double mu = pc.mu, fz_min = pc.fz_min, q = pc.q;
     __syncthreads();
-    // an invalid entry gives four NaNs (the rules of cmpc_solve_io_run); the same decision in
-    // every lane
-    if (__any(!(q >= 0.0 && isfinite(q) && r > 0.0 && isfinite(r))) ||
-        !(mu > 0.0 && isfinite(mu) && isfinite(fz_min))) {
+    // an invalid entry gives four NaNs; the same decision in every lane
+    if (!pc.valid) {
       if (lane < 4) a.res[b * 4 + lane] = __builtin_nan("");
       __syncthreads();
       continue;
@@ -206,7 +162,7 @@ __global__ void __launch_bounds__(64) kkt_kernel(KktArgs a, int64_t B) {
             acc = fma(-(double)sBd[(k * 12 + i) * 12 + j], Ld[k * 12 + i], acc);
           s[c] = acc;
         }
-        kkt_recover_leg(sC[leg * N + k] != 0, s, f[0], f[1], f[2], mu, fz_min, a.tol, lf, lx);
+        kkt_recover_leg(sC[leg * N + k] != 0, s, f[0], f[1], f[2], mu, fz_min, a.p.tol, lf, lx);
 #pragma unroll
         for (int c = 0; c < 3; ++c) Lx[12 * N + k * 12 + 3 * leg + c] = lx[c];
 #pragma unroll

@@ -1,7 +1,9 @@
 """A/B of two library builds for bit-identical results: solve the headline batch (config 3,
 65,536) cold and its next tick warm, config 2 at 4,096 cold, and small batches that walk the
 paths those miss (small_cases), with the library given, and write (w, status, iterations, and
-y / lam where a case returns them); run once per library in separate processes, then compare.
+y / lam where a case returns them, and what Plan.kkt and Plan.gain make of four of the small
+batches where the library has those entries); run once per library in separate processes, then
+compare.
     python tools/bitwise_ab.py LIB OUT.npz            (GPU)
     python tools/bitwise_ab.py --compare A.npz B.npz   (CPU)"""
 import sys
@@ -20,14 +22,16 @@ KEYS = ("Ad", "Bd", "gd", "x0", "xref", "contact")
 def small_cases(res):
     """Batches of at most ~1,000 instances, seconds each: team mode forced, cmpc_solve_ref, per-robot
     terrain (one invalid row) and weights, a primal-only warm start, an all-swing instance, N = 8,
-    and a general step matrix in every mode (general_cases: the fixtures above are all nilpotent)."""
+    a general step matrix in every mode (general_cases: the fixtures above are all nilpotent), and
+    the evaluation entries on four of those solves (evaluate)."""
     import torch
-    from cmpc import Plan, SolverParams, to_device_batch, synth
+    from cmpc import Plan, SolverParams, _lib, to_device_batch, synth
 
     def put(tag, r, extra=()):
         torch.cuda.synchronize()
         for k, v in zip(("w", "st", "it") + tuple(extra), r):
             res[f"{tag}_{k}"] = v.cpu().numpy()
+        return r
 
     def dev(np_batch):
         return to_device_batch({k: np.ascontiguousarray(np_batch[k]) for k in KEYS})
@@ -38,7 +42,24 @@ def small_cases(res):
     def f32(a):
         return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
 
+    def evaluate(tag, p, d, r, **kw):
+        """Plan.kkt with lam given and recovered, Plan.gain with every output, faces read off w
+        and then given, on the batch d solved with lam_out as r (kw: its per-robot values)."""
+        out, w, lam = {}, r[0], r[3]
+        if hasattr(p.lib, "cmpc_kkt_run"):
+            out["kkt_given"] = p.kkt(*args(d), w, lam=lam, **kw)
+            out["kkt_recovered"] = p.kkt(*args(d), w, **kw)
+        if hasattr(p.lib, "cmpc_gain_run"):
+            g = p.gain(*args(d), w=w, want=_lib.GAIN_OUTPUTS, **kw)
+            out.update({f"gain_w_{k}": v for k, v in g.items()})
+            g = p.gain(*args(d), faces=g["faces"], want=_lib.GAIN_OUTPUTS, **kw)
+            out.update({f"gain_faces_{k}": v for k, v in g.items()})
+        torch.cuda.synchronize()
+        res.update({f"{tag}_{k}": v.cpu().numpy() for k, v in out.items()})
+
     plan = Plan(SolverParams(max_batch=4096))
+    d = dev(np.load(GOLDEN / "qp_cfg1.npz"))
+    evaluate("cfg1_ref", plan, d, put("cfg1_ref", plan.solve(*args(d), lam_out=True), ("lam",)))
     # team mode forced, on the fixtures of every bin (y out: the dual writer in team mode)
     plan.set_team(1 << 40)
     for name in ("qp_cfg1", "qp_nc192", "qp_hard"):
@@ -59,19 +80,24 @@ def small_cases(res):
     ft = np.load(GOLDEN / "qp_terrain.npz")
     mu, fz = ft["mu_A"].copy(), ft["fz_min_A"].copy()
     mu[3] = -1.0
-    put("terrain", plan.solve(*args(dev(ft)), mu=f32(mu), fz_min=f32(fz), lam_out=True), ("lam",))
+    d, kw = dev(ft), dict(mu=f32(mu), fz_min=f32(fz))
+    evaluate("terrain", plan, d, put("terrain", plan.solve(*args(d), lam_out=True, **kw), ("lam",)), **kw)
     fw = np.load(GOLDEN / "qp_weights.npz")
     put("weights", plan.solve(*args(dev(fw)), Q=f32(fw["Q_A"]), R=f32(fw["R_A"]), y_out=True), ("y",))
     R = fw["R_B"].copy()
     R[5, 2] = 0.0
-    put("weights_bad_row", plan.solve(*args(dev(fw)), Q=f32(fw["Q_B"]), R=f32(R), lam_out=True), ("lam",))
+    d, kw = dev(fw), dict(Q=f32(fw["Q_B"]), R=f32(R))
+    evaluate("weights_bad_row", plan, d,
+             put("weights_bad_row", plan.solve(*args(d), lam_out=True, **kw), ("lam",)), **kw)
     # an all-swing instance among stance ones
     fc = {k: np.load(GOLDEN / "qp_cfg1.npz")[k].copy() for k in KEYS}
     fc["contact"][1] = 0
     put("all_swing", plan.solve(*args(dev(fc)), lam_out=True), ("lam",))
     # a plan with N = 8
     p8 = Plan(SolverParams(N=8, max_batch=1024))
-    put("n8", p8.solve(*args(dev(synth.make_batch(768, seed=11, mixed=True, N=8))), y_out=True), ("y",))
+    d = dev(synth.make_batch(768, seed=11, mixed=True, N=8))
+    put("n8", p8.solve(*args(d), y_out=True), ("y",))
+    evaluate("n8_ref", p8, d, put("n8_ref", p8.solve(*args(d), lam_out=True), ("lam",)))
     general_cases(plan, put, dev, args)
 
 
@@ -139,10 +165,11 @@ def compare(a, b):
     if sorted(A.files) != sorted(B.files):
         print("the two files hold different cases")
         ok = False
-    for k in A.files:
-        same = np.array_equal(A[k].view(np.uint32) if A[k].dtype == np.float32 else A[k],
-                              B[k].view(np.uint32) if B[k].dtype == np.float32 else B[k])
-        nd = int(np.sum(np.any((A[k] != B[k]).reshape(A[k].shape[0], -1), axis=1)))
+    for k in sorted(set(A.files) & set(B.files)):
+        # the arrays' bytes: equal NaN bit patterns (an invalid row's results) are equal
+        x, y = (np.ascontiguousarray(v[k]).reshape(len(v[k]), -1).view(np.uint8) for v in (A, B))
+        same = A[k].dtype == B[k].dtype and x.shape == y.shape and bool(np.all(x == y))
+        nd = int(np.any(x != y, axis=1).sum()) if x.shape == y.shape else "all"
         print(f"{k}: {'bit-identical' if same else f'{nd} instances differ'}")
         ok = ok and same
     print("ALL BIT-IDENTICAL" if ok else "DIFFERENT")

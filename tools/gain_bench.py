@@ -11,7 +11,6 @@ rollout (rounded to fp32, as the evaluation takes it) against that of w_out.
    usage: python tools/gain_bench.py [--batch 65536] [--rounds 10] [--warmup 3] [--reps 5]
                                      [--out profiles/gain_bench.json]"""
 import argparse
-import json
 import sys
 from pathlib import Path
 
@@ -19,10 +18,11 @@ REPO = Path(__file__).resolve().parents[1]
 for p in (REPO, REPO / "convex-mpc-unitree-go2_amd"):
     sys.path.insert(0, str(p))
 
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from cmpc import Plan, SolverParams, synth, to_device_batch  # noqa: E402
+
+from bench_util import emit, interleaved_rounds  # noqa: E402
 
 ALL = ("K", "Vx", "Vxx", "u_star", "faces")
 
@@ -33,20 +33,6 @@ def bytes_moved(N, everything):
     rd = 4 * (144 + 144 * N + 12 + 12 + 12 * N + 12 * N) + 4 * N
     wr = 8 * 144 + (8 * (12 + 144 + 12 * N) + 4 * N if everything else 0)
     return rd, wr
-
-
-def timed(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / reps
-
-
-def summary(ms):
-    return {"ms": float(np.median(ms)), "ms_min": float(min(ms)), "ms_max": float(max(ms))}
 
 
 def rollout_w(d, u_star, N):
@@ -93,15 +79,9 @@ def main():
         "solve_cold": (lambda: plan.solve(*args, out=out), 1),
         "solve_warm": (lambda: plan.solve(*args, out=out, w_init=w, y_init=y, y_out=y2), 1),
     }
-    ms = {k: [] for k in variants}
-    for r in range(a.warmup + a.rounds):
-        for k, (fn, reps) in variants.items():
-            t = timed(fn, reps)
-            if r >= a.warmup:
-                ms[k].append(t)
     rec = {"config": 3, "batch": B, "N": N, "rounds": a.rounds, "warmup": a.warmup, "reps": a.reps,
            "device": torch.cuda.get_device_name(dev)}
-    rec.update({k: summary(v) for k, v in ms.items()})
+    rec.update(interleaved_rounds(variants, a.warmup, a.rounds))
     for m in modes:
         k = rec["gain_" + m]
         rd, wr = bytes_moved(N, m == "all")
@@ -131,10 +111,7 @@ def main():
         "kkt_prim_u_star_rollout_fp32_max": float(k_ref[:, 2].max()),
         "cost_lower_on_u_star": int((k_ref[:, 0] < k_out[:, 0]).sum()),
     }
-    line = json.dumps(rec)
-    print(line)
-    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(a.out).write_text(line + "\n")
+    emit(rec, a.out)
 
 
 if __name__ == "__main__":

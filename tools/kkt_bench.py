@@ -10,7 +10,6 @@ evaluation reports for the batch (largest stat / prim / comp over status-1 answe
    usage: python tools/kkt_bench.py [--batch 65536] [--rounds 10] [--warmup 3] [--reps 20]
                                     [--out profiles/kkt_bench.json]"""
 import argparse
-import json
 import sys
 from pathlib import Path
 
@@ -23,24 +22,12 @@ import torch  # noqa: E402
 
 from cmpc import KKT_COLUMNS, Plan, SolverParams, synth, to_device_batch  # noqa: E402
 
+from bench_util import emit, interleaved_rounds  # noqa: E402
+
 
 def bytes_read(N, with_lam):
     """Bytes cmpc_kkt_run reads per instance: Ad, Bd, gd, x0, xref (fp32), contact, w (+ lam)."""
     return 4 * (144 + 144 * N + 12 + 12 + 12 * N + 24 * N + (52 * N if with_lam else 0)) + 4 * N
-
-
-def timed(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / reps
-
-
-def summary(ms):
-    return {"ms": float(np.median(ms)), "ms_min": float(min(ms)), "ms_max": float(max(ms))}
 
 
 def main():
@@ -73,15 +60,9 @@ def main():
         "copy_recovered": (lambda: dst["recovered"].copy_(src["recovered"]), a.reps),
         "solve_cold": (lambda: plan.solve(*args, out=out), 1),
     }
-    ms = {k: [] for k in variants}
-    for r in range(a.warmup + a.rounds):
-        for k, (fn, reps) in variants.items():
-            t = timed(fn, reps)
-            if r >= a.warmup:
-                ms[k].append(t)
     rec = {"config": 3, "batch": B, "N": N, "rounds": a.rounds, "warmup": a.warmup, "reps": a.reps,
            "device": torch.cuda.get_device_name(dev), "columns": list(KKT_COLUMNS)}
-    rec.update({k: summary(v) for k, v in ms.items()})
+    rec.update(interleaved_rounds(variants, a.warmup, a.rounds))
     ok = (st == 1).cpu().numpy()
     rec["status1"] = int(ok.sum())
     for m in ("given", "recovered"):
@@ -94,10 +75,7 @@ def main():
         v = plan.kkt(*args, w, lam=lam if m == "given" else None).cpu().numpy()
         k["status1_max"] = {c: float(v[ok, i].max()) for i, c in enumerate(KKT_COLUMNS) if i}
         k["status1_inf_comp"] = int(np.isinf(v[ok, 3]).sum())
-    line = json.dumps(rec)
-    print(line)
-    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(a.out).write_text(line + "\n")
+    emit(rec, a.out)
 
 
 if __name__ == "__main__":

@@ -4,7 +4,6 @@ arrays).  Prints and optionally writes one JSON record: ms per step, the status 
 the mean / max ADMM iterations of each.
    usage: python tools/terrain_bench.py [--batch 65536] [--steps 10] [--warmup 3] [--out FILE]"""
 import argparse
-import json
 import sys
 from pathlib import Path
 
@@ -12,36 +11,11 @@ REPO = Path(__file__).resolve().parents[1]
 for p in (REPO, REPO / "convex-mpc-unitree-go2_amd"):
     sys.path.insert(0, str(p))
 
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from cmpc import Plan, SolverParams, synth, to_device_batch  # noqa: E402
 
-
-def run(plan, d, steps, warmup, **kw):
-    B = d["Ad"].shape[0]
-    N = plan.params.N
-    out = (torch.empty((B, 24 * N), dtype=torch.float32, device=plan.device),
-           torch.empty((B,), dtype=torch.int32, device=plan.device),
-           torch.empty((B,), dtype=torch.int32, device=plan.device))
-    step = lambda: plan.solve(d["Ad"], d["Bd"], d["gd"], d["x0"], d["xref"], d["contact"],  # noqa: E731
-                              out=out, **kw)
-    for _ in range(warmup):
-        step()
-    torch.cuda.synchronize(plan.device)
-    ms = []
-    for _ in range(steps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        step()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    st, it = out[1].cpu().numpy(), out[2].cpu().numpy()
-    vals, cnt = np.unique(st, return_counts=True)
-    return {"ms_per_step": float(np.median(ms)), "ms_min": float(min(ms)), "ms_max": float(max(ms)),
-            "status": {str(int(v)): int(c) for v, c in zip(vals, cnt)},
-            "iters_mean": float(it.mean()), "iters_max": int(it.max())}
+from bench_util import emit, solve_steps  # noqa: E402
 
 
 def main():
@@ -59,14 +33,10 @@ def main():
     rec = {"config": 3, "batch": a.batch, "steps": a.steps, "warmup": a.warmup,
            "terrain": {"seed": a.seed, "mu": [0.2, 1.0], "fz_min": [0.0, 20.0]},
            "device": torch.cuda.get_device_name(plan.device),
-           "plan_constants": run(plan, d, a.steps, a.warmup),
-           "per_instance": run(plan, d, a.steps, a.warmup, mu=d["mu"], fz_min=d["fz_min"])}
+           "plan_constants": solve_steps(plan, d, a.steps, a.warmup),
+           "per_instance": solve_steps(plan, d, a.steps, a.warmup, mu=d["mu"], fz_min=d["fz_min"])}
     rec["ratio"] = rec["per_instance"]["ms_per_step"] / rec["plan_constants"]["ms_per_step"]
-    line = json.dumps(rec)
-    print(line)
-    if a.out:
-        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(a.out).write_text(line + "\n")
+    emit(rec, a.out)
 
 
 if __name__ == "__main__":

@@ -7,7 +7,6 @@ over (the run-to-run spread of the headline path, for an A/B against another bui
    usage: python tools/weights_bench.py [--batch 65536] [--steps 10] [--warmup 3] [--out FILE]
                                         [--null-only] [--repeat 1]"""
 import argparse
-import json
 import sys
 from pathlib import Path
 
@@ -15,36 +14,11 @@ REPO = Path(__file__).resolve().parents[1]
 for p in (REPO, REPO / "convex-mpc-unitree-go2_amd"):
     sys.path.insert(0, str(p))
 
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from cmpc import Plan, SolverParams, synth, to_device_batch  # noqa: E402
 
-
-def run(plan, d, steps, warmup, **kw):
-    B = d["Ad"].shape[0]
-    N = plan.params.N
-    out = (torch.empty((B, 24 * N), dtype=torch.float32, device=plan.device),
-           torch.empty((B,), dtype=torch.int32, device=plan.device),
-           torch.empty((B,), dtype=torch.int32, device=plan.device))
-    step = lambda: plan.solve(d["Ad"], d["Bd"], d["gd"], d["x0"], d["xref"], d["contact"],  # noqa: E731
-                              out=out, **kw)
-    for _ in range(warmup):
-        step()
-    torch.cuda.synchronize(plan.device)
-    ms = []
-    for _ in range(steps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        step()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    st, it = out[1].cpu().numpy(), out[2].cpu().numpy()
-    vals, cnt = np.unique(st, return_counts=True)
-    return {"ms_per_step": float(np.median(ms)), "ms_min": float(min(ms)), "ms_max": float(max(ms)),
-            "status": {str(int(v)): int(c) for v, c in zip(vals, cnt)},
-            "iters_mean": float(it.mean()), "iters_max": int(it.max())}
+from bench_util import emit, solve_steps  # noqa: E402
 
 
 def main():
@@ -62,7 +36,7 @@ def main():
     d = to_device_batch(batch, plan.device)
     rec = {"config": 3, "batch": a.batch, "steps": a.steps, "warmup": a.warmup,
            "device": torch.cuda.get_device_name(plan.device),
-           "plan_constants": [run(plan, d, a.steps, a.warmup) for _ in range(a.repeat)]}
+           "plan_constants": [solve_steps(plan, d, a.steps, a.warmup) for _ in range(a.repeat)]}
     if not a.null_only:
         wt = synth.make_weights(a.batch, a.seed)
         f32 = torch.float32
@@ -71,14 +45,10 @@ def main():
         Qc, Rc = (torch.tensor(v, dtype=f32).expand(a.batch, 12).contiguous().to(plan.device)
                   for v in (p.Q, p.R))
         rec["weights"] = {"seed": a.seed, "q_span": 4.0, "r": [2.5e-6, 1e-4]}
-        rec["constant_arrays"] = run(plan, d, a.steps, a.warmup, Q=Qc, R=Rc)
-        rec["per_instance"] = run(plan, d, a.steps, a.warmup, Q=Q, R=R)
+        rec["constant_arrays"] = solve_steps(plan, d, a.steps, a.warmup, Q=Qc, R=Rc)
+        rec["per_instance"] = solve_steps(plan, d, a.steps, a.warmup, Q=Q, R=R)
         rec["ratio"] = rec["per_instance"]["ms_per_step"] / rec["plan_constants"][0]["ms_per_step"]
-    line = json.dumps(rec)
-    print(line)
-    if a.out:
-        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(a.out).write_text(line + "\n")
+    emit(rec, a.out)
 
 
 if __name__ == "__main__":
