@@ -73,14 +73,23 @@ class CGainIO(ctypes.Structure):
                           "faces_out")
 
 
+class CVjpIO(ctypes.Structure):
+    """cmpc_vjp_io (include/cmpc.h): a batch whose gradients of a loss are wanted, given dL/dw,
+    with the per-instance values of CSolveIO.  ``size`` is this mirror's sizeof."""
+    _fields_ = _io_fields("Q", "R", "w", "faces", "face_tol", "gw", "g_x0", "g_xref", "g_gd", "g_Q",
+                          "g_R", "g_mu", "g_fz_min", "g_Ad", "g_Bd")
+
+
 # cmpc_gain_io's face-mask bits of a stance (step, leg): CMPC_FACE_*
 FACE_FZ_MIN, FACE_FX_POS, FACE_FX_NEG, FACE_FY_POS, FACE_FY_NEG = 1, 2, 4, 8, 16
 GAIN_OUTPUTS = ("K", "Vx", "Vxx", "u_star", "faces")
+# Plan.vjp's results: the input each gradient belongs to (field g_<name> of cmpc_vjp_io)
+VJP_OUTPUTS = ("x0", "xref", "gd", "Q", "R", "mu", "fz_min", "Ad", "Bd")
 
 KKT_COLUMNS = ("cost", "stat", "prim", "comp")  # CMPC_KKT_COST .. CMPC_KKT_COMP
 
 EXPORTS = ("cmpc_params_default", "cmpc_plan_create", "cmpc_solve", "cmpc_plan_destroy",
-           "cmpc_build_dynamics", "cmpc_solve_warm", "cmpc_solve_ref", "cmpc_solve_io_run", "cmpc_kkt_run", "cmpc_gain_run", "cmpc_generate_traj", "cmpc_leg_torque", "cmpc_srb_step",
+           "cmpc_build_dynamics", "cmpc_solve_warm", "cmpc_solve_ref", "cmpc_solve_io_run", "cmpc_kkt_run", "cmpc_gain_run", "cmpc_vjp_run", "cmpc_generate_traj", "cmpc_leg_torque", "cmpc_srb_step",
            "cmpc_plan_set_timing", "cmpc_plan_timing_read", "cmpc_plan_set_team", "cmpc_plan_team_batch",
            "cmpc_plan_set_heavy_first",
            "cmpc_plan_heavy_first_batch", "cmpc_plan_solve_kernel", "cmpc_plan_stats",
@@ -132,6 +141,9 @@ def load(path: str | Path | None = None) -> ctypes.CDLL:
     if hasattr(lib, "cmpc_gain_run"):  # absent from builds that predate the feedback gain
         lib.cmpc_gain_run.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(CGainIO), vp]
         lib.cmpc_gain_run.restype = ctypes.c_int
+    if hasattr(lib, "cmpc_vjp_run"):  # absent from builds that predate the backward pass
+        lib.cmpc_vjp_run.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(CVjpIO), vp]
+        lib.cmpc_vjp_run.restype = ctypes.c_int
     lib.cmpc_build_dynamics.argtypes = [vp, ctypes.c_int64, ctypes.c_float] + [vp] * 8
     lib.cmpc_build_dynamics.restype = ctypes.c_int
     if hasattr(lib, "cmpc_generate_traj"):

@@ -451,6 +451,63 @@ class Plan:
         _check(self.lib, rc, "cmpc_gain_run")
         return res
 
+    def vjp(self, Ad, Bd, gd, x0, xref, contact, gw, w=None, faces=None, mu=None, fz_min=None,
+            Q=None, R=None, face_tol=None, want=("x0",), out=None, stream=None):
+        """Gradients of a loss through B solved instances on the device (cmpc_vjp_run,
+        include/cmpc.h): the backward pass of the MPC as a differentiable layer.
+
+        ``Ad`` .. ``contact``, ``mu`` / ``fz_min`` / ``Q`` / ``R``, ``w`` / ``faces`` and
+        ``face_tol`` as for :meth:`gain`; ``gw`` (B, 24N) fp32 is dL/dw in w's layout, states
+        then forces.  ``want`` names the inputs whose gradient is wanted, a non-empty subset of
+        ``("x0", "xref", "gd", "Q", "R", "mu", "fz_min", "Ad", "Bd")``; work that only the others
+        need is skipped, and a result does not depend on what else is asked for.  Returns a dict
+        of float64 device tensors of the inputs' shapes (``Q`` / ``R`` (B, 12) and ``mu`` /
+        ``fz_min`` (B,) whether the values came from the plan or from a row).  The gradient is
+        that of the fp64 optimum on the held faces, the face set fixed (:meth:`gain`'s
+        ``u_star`` and its rollout).  An instance with an inconsistent mask or an invalid mu /
+        fz_min entry or Q / R row gets NaN.  ``out`` is a dict of preallocated tensors for some
+        or all of the wanted names.  Asynchronous on ``stream`` (default: torch's current
+        stream), no allocation when every wanted name is in ``out``, graph-capturable; the
+        inputs are not modified and B is not limited by max_batch."""
+        if not hasattr(self.lib, "cmpc_vjp_run"):
+            raise CmpcError("cmpc: this libcmpc.so has no cmpc_vjp_run: Plan.vjp needs a library "
+                            "built from sources that declare it")
+        want = tuple(want)
+        unknown = [n for n in want if n not in _lib.VJP_OUTPUTS]
+        if unknown or not want:
+            raise ValueError(f"vjp: want {want} must be a non-empty subset of {_lib.VJP_OUTPUTS}")
+        if w is None and faces is None:
+            raise ValueError("vjp needs w or faces: one must name the held faces")
+        N = self.params.N
+        B = Ad.shape[0]
+        if B < 1:
+            raise ValueError("vjp needs at least one instance")
+        f32, f64, u8 = torch.float32, torch.float64, torch.uint8
+        io = _lib.CVjpIO()
+        io.size = ctypes.sizeof(_lib.CVjpIO)
+        self._fill_io(io, dict(_problem_spec(B, N, Ad, Bd, gd, x0, xref, contact),
+                               gw=(gw, f32, (B, 24 * N))),
+                      dict(w=(w, f32, (B, 24 * N)), faces=(faces, u8, (B, N, 4)),
+                           **_instance_spec(B, mu, fz_min, Q, R)))
+        shapes = dict(x0=(B, 12), xref=(B, N, 12), gd=(B, 12), Q=(B, 12), R=(B, 12), mu=(B,),
+                      fz_min=(B,), Ad=(B, 12, 12), Bd=(B, N, 12, 12))
+        out = dict(out or {})
+        res = {}
+        for name in want:
+            t = out.get(name)
+            if t is None:
+                t = torch.empty(shapes[name], dtype=f64, device=Ad.device)
+            _dev_tensor(t, name, f64, shapes[name])
+            self._same_device(t)
+            setattr(io, "g_" + name, t.data_ptr())
+            res[name] = t
+        io.face_tol = 0.0 if face_tol is None else float(face_tol)
+        sp = _stream_ptr(stream, Ad.device)
+        with torch.cuda.device(Ad.device):
+            rc = self.lib.cmpc_vjp_run(self._h, ctypes.c_int64(B), ctypes.byref(io), sp)
+        _check(self.lib, rc, "cmpc_vjp_run")
+        return res
+
     def build_dynamics(self, mass, inertia, r_feet, xref, dt, out=None, stream=None):
         """Discrete dynamics (Ad, Bd, gd) of B robots on the device -- the reference's
         ComTraj._continuousDynamics + _discreteDynamics (com_trajectory.py:221-286) in closed

@@ -21,6 +21,7 @@
 #include "cmpc_sim.hip"       // single-rigid-body plant (closed-loop stand-in for MuJoCo)
 #include "cmpc_kkt.hip"       // cost and KKT residuals of a batch of points
 #include "cmpc_gain.hip"      // feedback gain and value function on the held faces
+#include "cmpc_vjp.hip"       // gradients of a loss through the optimum on the held faces
 
 constexpr int kNumGroups = 3;  // solve kernels (register classes), see solve_group_kernel
 static_assert(kNumGroups == CMPC_NUM_SOLVE_KERNELS, "one timing slot per solve kernel");
@@ -132,7 +133,7 @@ int io_copy(const IO* io, size_t min_size, const char* what, const char* type, I
   return CMPC_OK;
 }
 
-// The checks of an evaluation entry (cmpc_kkt_io, cmpc_gain_io) after io_copy: plan, B, the six
+// The checks of an evaluation entry (cmpc_kkt_io, cmpc_gain_io, cmpc_vjp_io) after io_copy: plan, B, the six
 // problem arrays, face_tol, the device.  `own`: the entry's own required arrays are there;
 // `between`: the message of a failed check of the entry's own that ranks after the arrays, or NULL.
 template <class IO>
@@ -465,6 +466,28 @@ int cmpc_gain_run(cmpc_plan* pl, int64_t B, const cmpc_gain_io* io, void* stream
                      (hipStream_t)stream, k, B, keep);  // one wave per instance
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "gain_kernel launch");
+  return CMPC_OK;
+}
+
+int cmpc_vjp_run(cmpc_plan* pl, int64_t B, const cmpc_vjp_io* io, void* stream) {
+  cmpc_vjp_io a;
+  if (int rc = io_copy(io, offsetof(cmpc_vjp_io, g_x0) + sizeof(io->g_x0), "cmpc_vjp_run",
+                       "cmpc_vjp_io", a))
+    return rc;
+  const bool any = a.g_x0 || a.g_xref || a.g_gd || a.g_Q || a.g_R || a.g_mu || a.g_fz_min ||
+                   a.g_Ad || a.g_Bd;
+  if (int rc = check_problem(pl, B, a, a.gw, "cmpc_vjp_run",
+                             !(a.w || a.faces) ? ": w and faces are both null (one must name the "
+                                                 "held faces)"
+                             : !any ? ": every output is null (one must be given)" : nullptr))
+    return rc;
+  const cmpc::VjpArgs k{problem_args(pl, a), a.faces ? nullptr : a.w, a.faces, a.gw, a.g_x0,
+                        a.g_xref, a.g_gd, a.g_Q, a.g_R, a.g_mu, a.g_fz_min, a.g_Ad, a.g_Bd};
+  const size_t dyn = (size_t)k.p.N * cmpc::kVjpSlot * sizeof(double);
+  hipLaunchKernelGGL(cmpc::vjp_kernel, dim3(grid_stride_blocks(B)), dim3(64), dyn,
+                     (hipStream_t)stream, k, B);  // one wave per instance
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "vjp_kernel launch");
   return CMPC_OK;
 }
 

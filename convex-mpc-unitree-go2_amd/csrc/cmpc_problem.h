@@ -1,7 +1,7 @@
-// cmpc_problem.h -- what the evaluation kernels next to the solver (cmpc_kkt.hip, cmpc_gain.hip)
-// share: the problem part of their argument blocks, its image in LDS, the staging of an instance
+// cmpc_problem.h -- what the evaluation kernels next to the solver (cmpc_kkt.hip, cmpc_gain.hip,
+// cmpc_vjp.hip) share: the problem part of their argument blocks, its image in LDS, the staging of an instance
 // into it, the instance's constants with the validity decision, and the face rule.
-// Included by those two files only; the solve kernels have their own inputs and an fp32 face
+// Included by those files only; the solve kernels have their own inputs and an fp32 face
 // rule with a slack (cmpc_device.h, cmpc_wave.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -11,7 +11,7 @@
 
 namespace cmpc {
 
-// the leading fields of KktArgs and GainArgs
+// the leading fields of KktArgs, GainArgs and VjpArgs
 struct ProblemArgs {
   int N;
   float Q2[12], R2[12];  // the plan's constants: 2Q, 2R

@@ -333,6 +333,68 @@ typedef struct cmpc_gain_io {
 #define CMPC_FACE_FY_NEG 16
 int cmpc_gain_run(cmpc_plan* plan, int64_t B, const cmpc_gain_io* io, void* stream);
 
+/* Gradients of a loss through B solved instances (the backward pass of a differentiable MPC
+ * layer), on the device.  The function differentiated is the one cmpc_gain_run solves: for every
+ * instance w*(theta) = (x_1..x_N, u_0..u_{N-1}) is the minimiser of 1/2 w'Hw + g'w over the
+ * dynamics and the held faces, the face set fixed -- cmpc_gain_io's u_star and its rollout.
+ * Given gw = dL/dw for any loss L on that solution, the entry returns dL/dtheta for every input
+ * a policy or an estimator can set.  Write the restricted QP as [[H, E'], [E, 0]] [w; nu] =
+ * [-g; b], E holding the dynamics rows x_{k+1} - Ad x_k - Bd_k u_k = gd (multipliers nu_k), the
+ * held face rows (fz = fz_min;  fx - mu fz = 0 on a +mu face, fx + mu fz = 0 on a -mu face; the
+ * same for fy) and f = 0 on swing legs, and solve [[H, E'], [E, 0]] [dw; dnu] = [-gw; 0].  With
+ * x_0 = x0 and dx_0 = 0:
+ *   g_x0     [B][12]          -Ad' dnu_0
+ *   g_xref   [B][N][12]       -2Q o dx_{k+1}
+ *   g_gd     [B][12]          -sum_k dnu_k
+ *   g_Q      [B][12]          2 sum_k dx_{k+1} o (x_{k+1} - xref_k)
+ *   g_R      [B][12]          2 sum_k du_k o u_k
+ *   g_mu     [B]              sum over held friction rows r of a leg of sigma_r (nu_r dfz +
+ *                             dnu_r fz), sigma = -1 on a +mu face and +1 on a -mu face, fz / dfz
+ *                             that leg's entries of w* / dw
+ *   g_fz_min [B]              -sum dnu_r over held fz = fz_min rows
+ *   g_Ad     [B][12][12]      -sum_k (nu_k dx_k' + dnu_k x_k')
+ *   g_Bd     [B][N][12][12]   -(nu_k du_k' + dnu_k u_k')
+ * All fp64, all nullable, at least one required (else CMPC_E_INVALID); work that only outputs
+ * not asked for need is skipped, and an output is bit for bit the same whichever others are
+ * asked for.  g_Q and g_R are the gradients in the weight diagonals of the instance, whether
+ * they came from the plan or from a Q / R row; g_mu and g_fz_min likewise.  A leg that holds
+ * both signs of an axis is pinned at fz = 0 whatever mu and fz_min are (cmpc_gain_io's mask
+ * rule) and contributes nothing to g_mu and g_fz_min.
+ *   Ad..contact, mu, fz_min, Q, R, w, faces, face_tol   as in cmpc_gain_io; w and faces both
+ *                             NULL: CMPC_E_INVALID
+ *   gw       [B][24N]  fp32   required; dL/dw in w_out's layout, states then forces, widened
+ *                             exactly
+ * The gradient is that of the fp64 optimum on the faces named, not of the fp32 w_out, and it
+ * does not see a change of the face set.  An instance with an inconsistent mask, or with a mu /
+ * fz_min entry or Q / R row that is invalid by the rules of cmpc_solve_io, gets NaN in every
+ * output; it never fails the call and the other instances are unaffected.
+ * `size` is the caller's sizeof of the struct (fields past it read as NULL or 0); it must reach
+ * past `g_x0`.  B >= 1; no workspace is used, so the plan's max_batch does not limit B.  Each
+ * sum runs in a fixed order: the results are bitwise repeatable and do not depend on B or on the
+ * instance's place in the batch.  Same guarantees as cmpc_solve: asynchronous on `stream`, no
+ * allocation, no host synchronisation, graph-capturable; the plan's device must be current. */
+typedef struct cmpc_vjp_io {
+  uint32_t size;            /* sizeof of this struct in the caller's header */
+  const float *Ad, *Bd, *gd, *x0, *xref;  /* as cmpc_solve */
+  const uint8_t* contact;
+  const float *mu, *fz_min; /* [B] nullable: the plan's constants */
+  const float *Q, *R;       /* [B][12] nullable */
+  const float* w;           /* [B][24N] nullable: the point whose held faces define w* */
+  const uint8_t* faces;     /* [B][N][4] nullable: held faces given by the caller */
+  float face_tol;           /* used when faces == NULL; 0 selects 1e-6 */
+  const float* gw;          /* [B][24N] dL/dw, required */
+  double* g_x0;             /* [B][12] nullable, as every output */
+  double* g_xref;           /* [B][N][12] */
+  double* g_gd;             /* [B][12] */
+  double* g_Q;              /* [B][12] */
+  double* g_R;              /* [B][12] */
+  double* g_mu;             /* [B] */
+  double* g_fz_min;         /* [B] */
+  double* g_Ad;             /* [B][12][12] */
+  double* g_Bd;             /* [B][N][12][12] */
+} cmpc_vjp_io;
+int cmpc_vjp_run(cmpc_plan* plan, int64_t B, const cmpc_vjp_io* io, void* stream);
+
 void cmpc_plan_destroy(cmpc_plan* plan);
 
 /* QP data on the device: the reference's discrete dynamics
