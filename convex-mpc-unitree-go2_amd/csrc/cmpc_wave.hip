@@ -1064,7 +1064,8 @@ __device__ __forceinline__ void ldl_apply(SM& s, const f4 (&M)[Cfg<NC>::NTL], in
 #pragma unroll
     for (int q = 0; q < 4; ++q) zr[q] = (16 * I + 4 * g + q < n) ? zr[q] : 0.f;
     // the block turns from rows to columns through `out` (a register turn -- DPP / permlane
-    // swaps -- measured 1.3 % slower with this arithmetic, round 5)
+    // swaps -- measured 1.3 % slower with this arithmetic, round 5; for the one-wave class alone
+    // no gain on its kernel or on the step, profiles/heavy_paths_ab.txt)
     if (c == 0) *reinterpret_cast<f4*>(&out[16 * I + 4 * g]) = zr;
     WSYNC();
     zc[I] = out[16 * I + c];
@@ -1146,8 +1147,9 @@ __device__ __forceinline__ void gradient_powers(SM& s, f4 (&pw)[4], f4 (&tw)[4])
   }
 }
 
-// LAT (team / latency mode): the powers come precomputed (one set per instance, `pwc`/`twc`),
-// and the per-step B~ v sum is unrolled to the 12 params a step can hold so that its LDS reads
+// LAT (latency mode, kGradLat below): the powers come precomputed where the caller has them (team
+// mode, NC <= 128: one set per instance, `pwc`/`twc`; else they are built here as in the rolled
+// form), and the per-step B~ v sum is unrolled to the 12 params a step can hold so that its LDS reads
 // issue together (with two busy waves per SIMD the rolled loop measured faster: issue-bound)
 //
 // PREC (the polish: refinement and KKT check): the rollout e_{k+1} in float64.  Its inputs are
@@ -1159,6 +1161,15 @@ __device__ __forceinline__ void gradient_powers(SM& s, f4 (&pw)[4], f4 (&tw)[4])
 // exact) the noise is ~5e-9; e is rounded to fp32 once and the adjoint stays fp32 (NumPy
 // study: only the rollout needs the precision).  Nilpotent step only; the general A keeps the
 // fp32 rollout and the relative multiplier tolerance (polish_check).
+//
+// Which form a kernel runs (the FMA order per lane is the same in both, so the results are
+// bit-identical): the team kernels and the one-wave-per-SIMD wave kernel of NC 144 / 160
+// (Cfg::WPE == 1: nothing else on the SIMD hides the rolled loop's LDS round trips; its kernel
+// time -2.5 %, profiles/heavy_paths_ab.txt) take LAT.  The two-wave class keeps the rolled loop
+// (issue-bound), and so does the NC 192 kernel, where LAT's 39 live operands raise the spills
+// from 40 to 57 VGPRs and a standing batch gains nothing.
+template <int NC, int W>
+constexpr bool kGradLat = W > 1 || (Cfg<NC>::WPE == 1 && NC <= 160);
 template <int NC, bool LAT = false, bool PREC = false>
 __device__ __forceinline__ void gradient(Smem<NC>& s, const KParams& P, int n, const float* vin,
                                          float* gout, const f4* pwc = nullptr,
@@ -1432,12 +1443,31 @@ __device__ __forceinline__ int project(float a, float b, float c, float mu, floa
 // ADMM basis: every stance triple contributes (fx, fy, fz) as params 3t, 3t+1, 3t+2
 template <int NC>
 __device__ __forceinline__ void build_admm_basis(Smem<NC>& s, const KParams& P,
-                                                 const float* __restrict__ Bg, int ntri) {
+                                                 const float* __restrict__ Bg, int ntri,
+                                                 const float (*bw)[36] = nullptr,
+                                                 unsigned long long stance = 0) {
   const int lane = opaque_lane();
   const int N = P.N;
   const int n = 3 * ntri;
   WSYNC();
-  if (lane < ntri) {  // lane t copies the 12x3 block of its triple (all loads in flight at once)
+  if (bw != nullptr) {  // (a compile-time constant at every call site)
+    // stage_instance's first-touch rows: lane l holds rows 3 (l & 3) .. + 2 of step l >> 2, all 12
+    // columns.  It scatters the three columns of each stance leg of its step to that leg's
+    // triple, whose index is the count of stance (step, leg) pairs before it in `stance`.
+    const int k = lane >> 2, r0 = 3 * (lane & 3);
+#pragma unroll
+    for (int leg = 0; leg < 4; ++leg) {
+      const int bit = 4 * k + leg;
+      if ((stance >> bit) & 1ull) {
+        const int t = __popcll(stance & ((1ull << bit) - 1ull));
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+#pragma unroll
+          for (int rr = 0; rr < 3; ++rr) s.Bt[(3 * t + a) * kBS + r0 + rr] = (*bw)[rr * 12 + 3 * leg + a];
+        }
+      }
+    }
+  } else if (lane < ntri) {  // lane t copies the 12x3 block of its triple (all loads in flight at once)
     const int kl = s.tri[lane];
     const float* src = Bg + (kl >> 2) * 144 + 3 * (kl & 3);
     float bv[36];
@@ -2046,6 +2076,22 @@ __device__ __forceinline__ void stage_instance(Smem<NC>& s, const KParams& P, co
   const uint8_t* ctb = in.contact + b * (int64_t)4 * N;
 
   WSYNC();
+  // First touch: everything the staging reads from global memory goes out in ONE round.  The
+  // contact byte of (step, leg) = lane, and the instance's whole Bd as rows: lane l takes rows
+  // 3 (l & 3) .. + 2 of step l >> 2, 36 consecutive floats (every byte of a fetched line is
+  // used; the per-triple copy fetched 12-byte pieces 48 bytes apart, and only after the contact
+  // scan had gone through the LDS).  build_admm_basis scatters the stance columns from these
+  // registers once the scan is done; the tile registers are dead here, so they are free.
+  const uint8_t ctv = (lane < 4 * N) ? ctb[(lane & 3) * N + (lane >> 2)] : (uint8_t)0;
+  float bw[36];
+  if (lane < 4 * N) {
+    const float* src = Bg + lane * 36;
+#pragma unroll
+    for (int i = 0; i < 36; ++i) bw[i] = src[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 36; ++i) bw[i] = 0.f;
+  }
   {  // one round of global loads: A, r_0..r_N (= x0, xref), gd; staged in LDS (G is free here)
     float av[3], rv[4];
 #pragma unroll
@@ -2089,7 +2135,7 @@ __device__ __forceinline__ void stage_instance(Smem<NC>& s, const KParams& P, co
   // stance triples in (k, leg) order; lane = 4k + leg.  An instance whose mu / fz_min entry or
   // Q / R row is invalid has no problem to solve: it takes the all-swing path (zero forces,
   // X = the rollout) and returns status -10
-  const bool stc = (lane < 4 * N && terrain_valid(T) && weights_ok) ? (ctb[(lane & 3) * N + (lane >> 2)] != 0) : false;
+  const bool stc = lane < 4 * N && terrain_valid(T) && weights_ok && ctv != 0;
   const int pos = wave_excl_scan4(stc ? 1 : 0);
   const int ntri = wave_total4(stc ? 1 : 0);
   if (stc) s.tri[pos] = lane;
@@ -2104,7 +2150,7 @@ __device__ __forceinline__ void stage_instance(Smem<NC>& s, const KParams& P, co
       for (int j = 0; j < 12; ++j) acc = fmaf(s.A[r * 12 + j], rk[j], acc);
       s.D[o] = acc;
     }
-    build_admm_basis<NC>(s, P, Bg, ntri);
+    build_admm_basis<NC>(s, P, Bg, ntri, &bw, __ballot(stc));
   }
   const bool nil = nilpotent_step(s);  // A = I + N, N^2 = 0: the closed-form condensation
   if (lane == 0) s.nil = nil ? 1 : 0;   // (and the gradient's powers of A)
@@ -2258,7 +2304,7 @@ __device__ __forceinline__ Refined polish_refine(Smem<NC>& s, const KParams& P, 
     // (an extra pass -- ambiguous face multipliers, below -- is one more refinement step)
     for (int q = pass == 0 ? 0 : P.polish_refine + kRefineExtra - 1;
          q < P.polish_refine + kRefineExtra; ++q) {
-      gradient<NC, (W > 1), true>(s, P, nact, s.v, s.g, I.pwc, I.twc);
+      gradient<NC, kGradLat<NC, W>, true>(s, P, nact, s.v, s.g, I.pwc, I.twc);
       if constexpr (W == 1) {
         minv_apply<NC>(s, P, M, nact, s.g, s.dl);
         if (c.nadd > 0) dd_apply<NC>(s, nact, c.nadd, s.g, s.dl);  // (uniform)
@@ -2279,7 +2325,7 @@ __device__ __forceinline__ Refined polish_refine(Smem<NC>& s, const KParams& P, 
       if (q + 1 >= qmin && (r.step <= P.polish_tol * wave_max(mv) || r.stalled)) break;
       prev = r.step;
     }
-    gradient<NC, (W > 1), true>(s, P, nact, s.v, s.g, I.pwc, I.twc);  // E, L at the final point
+    gradient<NC, kGradLat<NC, W>, true>(s, P, nact, s.v, s.g, I.pwc, I.twc);  // E, L at the final point
     // a hard instance's later repairs move only the worst triples: full primal-dual
     // active-set steps swap several faces at a time and can wander between neighbouring sets
     const int top = (kRepairTop > 0 && (c.nfail > 0 || c.ntried >= 3)) ? kRepairTop : 0;
@@ -2530,7 +2576,7 @@ __device__ __forceinline__ bool admm_iteration(Smem<NC>& s, const KParams& P, co
   const Terrain T = I.T;
   const float alpha = P.alpha;
   float rho = c.rho;
-  gradient<NC, (W > 1)>(s, P, n, s.x, s.g, I.pwc, I.twc);
+  gradient<NC, kGradLat<NC, W>>(s, P, n, s.x, s.g, I.pwc, I.twc);
   {
     const int l = opaque_lane();
     if (l < ntri) {
@@ -2680,7 +2726,7 @@ __device__ __forceinline__ void write_y(Smem<NC>& s, const KParams& P, const Ins
   const int NP = I.NP;
   if (polished && I.n > 0) {  // y = -grad f(u*) (the ADMM fixed point); s.g is the reduced one
     build_admm_basis<NC>(s, P, I.Bg, I.ntri);
-    gradient<NC, (W > 1)>(s, P, I.n, s.x, s.g, I.pwc, I.twc);
+    gradient<NC, kGradLat<NC, W>>(s, P, I.n, s.x, s.g, I.pwc, I.twc);
   }
   const float* yf = polished ? s.g : s.y;
   const float sg = polished ? -1.f : 1.f;
@@ -2825,7 +2871,7 @@ __device__ __forceinline__ void solve_instance(Smem<NC>& s, const KParams& P, in
       const bool conv = c.rp <= P.eps_abs + P.eps_rel * c.np_ && c.rd <= P.eps_abs + P.eps_rel * c.nd;
       c.status = conv ? 2 : -2;
     }
-    gradient<NC, (W > 1)>(s, P, n, s.z, s.g, I.pwc, I.twc);  // E at u = z (the pure rollout when every leg swings)
+    gradient<NC, kGradLat<NC, W>>(s, P, n, s.z, s.g, I.pwc, I.twc);  // E at u = z (the pure rollout when every leg swings)
   }
   TRACEF(b, "END status %d iters %d\n", c.status, c.iters);
   CMPC_T0(t_out);
