@@ -49,8 +49,10 @@ class CParams(ctypes.Structure):
 def _io_fields(*names):
     """``size``, the arrays and values every io struct opens with, then the named fields."""
     head = ("Ad", "Bd", "gd", "x0", "xref", "contact", "mu", "fz_min")
+    values = dict(face_tol=ctypes.c_float, prim_tol=ctypes.c_float, dual_tol=ctypes.c_float,
+                  max_rounds=ctypes.c_int32)
     return ([("size", ctypes.c_uint32)] +
-            [(n, ctypes.c_float if n == "face_tol" else ctypes.c_void_p) for n in head + names])
+            [(n, values.get(n, ctypes.c_void_p)) for n in head + names])
 
 
 class CSolveIO(ctypes.Structure):
@@ -80,6 +82,17 @@ class CVjpIO(ctypes.Structure):
                           "g_R", "g_mu", "g_fz_min", "g_Ad", "g_Bd")
 
 
+class CRefineIO(ctypes.Structure):
+    """cmpc_refine_io (include/cmpc.h): a batch of answers to refine and certify in float64, with
+    the per-instance values of CSolveIO.  ``size`` is this mirror's sizeof."""
+    _fields_ = _io_fields("Q", "R", "w", "faces", "face_tol", "max_rounds", "prim_tol", "dual_tol",
+                          "info", "res", "w64", "lam_out", "faces_out", "w_out", "status")
+
+
+# cmpc_refine_io's info values below zero (CMPC_REFINE_*) and the results Plan.refine can return
+REFINE_INVALID, REFINE_ROUNDS, REFINE_CYCLE, REFINE_MAX_ROUNDS = -1, -2, -3, 16
+REFINE_OUTPUTS = ("info", "res", "w64", "lam", "faces")
+
 # cmpc_gain_io's face-mask bits of a stance (step, leg): CMPC_FACE_*
 FACE_FZ_MIN, FACE_FX_POS, FACE_FX_NEG, FACE_FY_POS, FACE_FY_NEG = 1, 2, 4, 8, 16
 GAIN_OUTPUTS = ("K", "Vx", "Vxx", "u_star", "faces")
@@ -89,7 +102,7 @@ VJP_OUTPUTS = ("x0", "xref", "gd", "Q", "R", "mu", "fz_min", "Ad", "Bd")
 KKT_COLUMNS = ("cost", "stat", "prim", "comp")  # CMPC_KKT_COST .. CMPC_KKT_COMP
 
 EXPORTS = ("cmpc_params_default", "cmpc_plan_create", "cmpc_solve", "cmpc_plan_destroy",
-           "cmpc_build_dynamics", "cmpc_solve_warm", "cmpc_solve_ref", "cmpc_solve_io_run", "cmpc_kkt_run", "cmpc_gain_run", "cmpc_vjp_run", "cmpc_generate_traj", "cmpc_leg_torque", "cmpc_srb_step",
+           "cmpc_build_dynamics", "cmpc_solve_warm", "cmpc_solve_ref", "cmpc_solve_io_run", "cmpc_kkt_run", "cmpc_gain_run", "cmpc_vjp_run", "cmpc_refine_run", "cmpc_generate_traj", "cmpc_leg_torque", "cmpc_srb_step",
            "cmpc_plan_set_timing", "cmpc_plan_timing_read", "cmpc_plan_set_team", "cmpc_plan_team_batch",
            "cmpc_plan_set_heavy_first",
            "cmpc_plan_heavy_first_batch", "cmpc_plan_solve_kernel", "cmpc_plan_stats",
@@ -144,6 +157,9 @@ def load(path: str | Path | None = None) -> ctypes.CDLL:
     if hasattr(lib, "cmpc_vjp_run"):  # absent from builds that predate the backward pass
         lib.cmpc_vjp_run.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(CVjpIO), vp]
         lib.cmpc_vjp_run.restype = ctypes.c_int
+    if hasattr(lib, "cmpc_refine_run"):  # absent from builds that predate the refinement
+        lib.cmpc_refine_run.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(CRefineIO), vp]
+        lib.cmpc_refine_run.restype = ctypes.c_int
     lib.cmpc_build_dynamics.argtypes = [vp, ctypes.c_int64, ctypes.c_float] + [vp] * 8
     lib.cmpc_build_dynamics.restype = ctypes.c_int
     if hasattr(lib, "cmpc_generate_traj"):

@@ -508,6 +508,76 @@ class Plan:
         _check(self.lib, rc, "cmpc_vjp_run")
         return res
 
+    def refine(self, Ad, Bd, gd, x0, xref, contact, w=None, faces=None, mu=None, fz_min=None,
+               Q=None, R=None, face_tol=0.0, max_rounds=8, prim_tol=0.0, dual_tol=0.0, w_out=None,
+               status=None, want=("info", "res"), out=None, stream=None):
+        """Certified float64 refinement of B solved instances on the device (cmpc_refine_run,
+        include/cmpc.h): a primal-dual active-set loop around :meth:`gain`'s ``u_star`` that
+        replaces an answer only when the float64 KKT conditions hold on the whole QP.
+
+        ``Ad`` .. ``contact``, ``mu`` / ``fz_min`` / ``Q`` / ``R``, ``w`` / ``faces`` and
+        ``face_tol`` (0 = 1e-6) as for :meth:`gain`; with ``faces`` given, ``w`` is still the
+        answer the error is measured from.  ``max_rounds`` (0..16) limits the repairs, 0 checks
+        only; ``prim_tol`` / ``dual_tol`` (0 = 1e-9) are the relative thresholds of a violated
+        face and of a negative multiplier.  ``w_out`` (B, 24N) fp32, which may be ``w`` itself,
+        receives the fp32 rounding of the certified point in the rows that were certified and
+        is left untouched, bit for bit, in every other row; ``status`` (B,) int32 is set to 1 in
+        the certified rows and left untouched otherwise.  ``want`` names the results, a subset
+        of ``("info", "res", "w64", "lam", "faces")``; ``info`` is always computed.  Returns a
+        dict of device tensors: ``info`` (B,) int32, r >= 0 = certified after r repairs,
+        ``_lib.REFINE_INVALID`` / ``REFINE_ROUNDS`` / ``REFINE_CYCLE`` otherwise; ``res`` (B, 3)
+        float64, the largest violation / us, the most negative held multiplier / gs and
+        max|u - u_in| / max(1, max|u_in|) (NaN without ``w``), on a certified row the measured
+        error of the answer given; ``w64`` (B, 24N) float64 the last round's point; ``lam``
+        (B, 52N) float64 its multipliers ``[lam_x | lam_a]`` in the layout of a solve's
+        ``lam_out``; ``faces`` (B, N, 4) uint8 its masks.  An invalid instance (an invalid mu /
+        fz_min entry or Q / R row, a given mask with both signs of an axis) gets NaN (0xFF in
+        ``faces``).  ``out`` is a dict of preallocated tensors for some or all of the wanted
+        names.  Asynchronous on ``stream`` (default: torch's current stream), no allocation when
+        every wanted name is in ``out``, graph-capturable; B is not limited by max_batch."""
+        if not hasattr(self.lib, "cmpc_refine_run"):
+            raise CmpcError("cmpc: this libcmpc.so has no cmpc_refine_run: Plan.refine needs a "
+                            "library built from sources that declare it")
+        want = tuple(want)
+        unknown = [n for n in want if n not in _lib.REFINE_OUTPUTS]
+        if unknown:
+            raise ValueError(f"refine: unknown result {unknown}; choose from {_lib.REFINE_OUTPUTS}")
+        if w is None and faces is None:
+            raise ValueError("refine needs w or faces: one must name the held faces")
+        N = self.params.N
+        B = Ad.shape[0]
+        if B < 1:
+            raise ValueError("refine needs at least one instance")
+        f32, f64, u8, i32 = torch.float32, torch.float64, torch.uint8, torch.int32
+        io = _lib.CRefineIO()
+        io.size = ctypes.sizeof(_lib.CRefineIO)
+        self._fill_io(io, _problem_spec(B, N, Ad, Bd, gd, x0, xref, contact),
+                      dict(w=(w, f32, (B, 24 * N)), faces=(faces, u8, (B, N, 4)),
+                           w_out=(w_out, f32, (B, 24 * N)), status=(status, i32, (B,)),
+                           **_instance_spec(B, mu, fz_min, Q, R)))
+        spec = dict(info=("info", i32, (B,)), res=("res", f64, (B, 3)),
+                    w64=("w64", f64, (B, 24 * N)), lam=("lam_out", f64, (B, 52 * N)),
+                    faces=("faces_out", u8, (B, N, 4)))
+        out = dict(out or {})
+        res = {}
+        for name in ("info",) + tuple(n for n in want if n != "info"):
+            field, dtype, shape = spec[name]
+            t = out.get(name)
+            if t is None:
+                t = torch.empty(shape, dtype=dtype, device=Ad.device)
+            _dev_tensor(t, name, dtype, shape)
+            self._same_device(t)
+            setattr(io, field, t.data_ptr())
+            res[name] = t
+        io.face_tol = float(face_tol)
+        io.max_rounds = int(max_rounds)
+        io.prim_tol, io.dual_tol = float(prim_tol), float(dual_tol)
+        sp = _stream_ptr(stream, Ad.device)
+        with torch.cuda.device(Ad.device):
+            rc = self.lib.cmpc_refine_run(self._h, ctypes.c_int64(B), ctypes.byref(io), sp)
+        _check(self.lib, rc, "cmpc_refine_run")
+        return res
+
     def build_dynamics(self, mass, inertia, r_feet, xref, dt, out=None, stream=None):
         """Discrete dynamics (Ad, Bd, gd) of B robots on the device -- the reference's
         ComTraj._continuousDynamics + _discreteDynamics (com_trajectory.py:221-286) in closed

@@ -96,6 +96,151 @@ __device__ inline double gain_rcp(double x) {
   return fma(r, fma(-x, r, 1.0), r);
 }
 
+// The LDS arrays of the backward recursion next to the staged problem
+struct GainLds {
+  const float *Zx, *Zy;       // per (step, leg): +-mu or 0, exact
+  const double *Cv, *D, *Dv;  // per step: c_k, diag(Z'RZ), d_k = Bd_k c_k + gd
+  double* P;                  // [144] P_k as computed (not yet mirrored); zero (P_N) on entry
+  double *GM, *Y;             // [12 * 25] [G | rhs], 16-byte aligned; [12 * 13] [Kp | kp]
+  double* K;                  // keep_steps ? N : 1 slots of (K_k [12][12], kappa_k [12])
+};
+
+// The backward recursion of the header's comment over the steps N-1 .. 0 for the whole wave:
+// leaves (K_k, kappa_k) in the slots of s.K, P_0 (not mirrored) in s.P and q_0 in qreg on the
+// lanes with (lane & 15) == 12 (entry (lane >> 4) + 4 r in qreg[r]).  The caller's barrier
+// stands before the call; the last step's barrier ends it.  gain_kernel and refine_kernel
+// (cmpc_refine.hip) both run it.
+__device__ __forceinline__ void gain_recursion(ProblemLds& sp, const GainLds& s, int N,
+                                               int keep_steps, int lane, double qreg[3]) {
+  auto& [sBd, sAd, sXr, sGX, sQ, sR, sC] = sp;
+  const float *const sZx = s.Zx, *const sZy = s.Zy;
+  const double *const sCv = s.Cv, *const sD = s.D, *const sDv = s.Dv;
+  double *const sP = s.P, *const sGM = s.GM, *const sY = s.Y, *const sK = s.K;
+  // ---- backward Riccati recursion on the f64 matrix cores.  Lane (c, g) = (lane & 15,
+  // lane >> 4) holds, of a 12x12 matrix X padded to 16x16, the three entries X[4q + g][c]:
+  // that is the B operand of X (pass q carries k = 4q + g), the A operand of X', and the
+  // layout a product comes out in (row g + 4 reg, column c) -- so products chain from
+  // register to register.  Column 12 of the B side carries the affine part (d, s, kappa, q).
+  const int c = lane & 15, g = lane >> 4;
+  const int cl = min(c, 11), cleg = cl / 3, cax = cl - 3 * cleg;
+  double adg[3];  // [Ad | gd] in that layout; qreg: q_{k+1} on lanes c == 12
+#pragma unroll
+  for (int q_ = 0; q_ < 3; ++q_) {
+    const int rq = 4 * q_ + g;
+    adg[q_] = c < 12 ? (double)sAd[rq * 12 + c] : (c == 12 ? (double)sGX[rq] : 0.0);
+    qreg[q_] = 0.0;
+  }
+  for (int k = N - 1; k >= 0; --k) {
+    const float* const Bk = sBd + k * 144;
+    const double* const Dk = sD + k * 12;
+    double* const Kk = sK + (keep_steps ? k : 0) * kGainSlot;
+    const bool used = c < 12 && Dk[cl] != 0.0;
+    double sa[3], bt[3], wv[3], ab[3], sreg[3];
+#pragma unroll
+    for (int q_ = 0; q_ < 3; ++q_) {
+      const int rq = 4 * q_ + g;
+      // S = Q + P_{k+1}, mirrored here: A operand S[c][rq]
+      const double sym = 0.5 * (sP[cl * 12 + rq] + sP[rq * 12 + cl]) + (cl == rq ? sQ[cl] : 0.0);
+      sa[q_] = c < 12 ? sym : 0.0;
+      // Bt = Bd_k Z: column c is slot c of leg cleg
+      const float* const bi = Bk + rq * 12 + 3 * cleg;
+      const double v = cax == 2 ? fma((double)sZx[k * 4 + cleg], (double)bi[0],
+                                      fma((double)sZy[k * 4 + cleg], (double)bi[1], (double)bi[2]))
+                                : (double)bi[cax];
+      bt[q_] = used ? v : 0.0;
+      wv[q_] = c == 12 ? sDv[k * 12 + rq] : adg[q_];  // [Ad | d_k], 0 past column 12
+      ab[q_] = c < 12 ? (double)Bk[cl * 12 + rq] : 0.0;  // A operand Bd_k[c][rq]
+      sreg[q_] = qreg[q_] - sQ[rq] * (double)sXr[k * 12 + rq];  // s, used on lanes c == 12
+    }
+    const gain_d4 zero = {0.0, 0.0, 0.0, 0.0};
+    gain_d4 SW = gain_mm(sa, wv, zero);  // [S Ad | S d]
+    gain_d4 SB = gain_mm(sa, bt, zero);  // S Bt
+    double swb[3], sbb[3];
+#pragma unroll
+    for (int r_ = 0; r_ < 3; ++r_) {
+      swb[r_] = c == 12 ? SW[r_] + sreg[r_] : SW[r_];  // column 12: S d + s
+      sbb[r_] = SB[r_];
+    }
+    gain_d4 G = gain_mm(bt, sbb, zero);  // Bt'S Bt
+    gain_d4 M = gain_mm(bt, swb, zero);  // [Bt'S Ad | Bt'(S d + s)]
+    // [G | M] to LDS, G = Bt'S Bt + D with 1 on the diagonal of a slot not in use
+    if (c < 13) {
+#pragma unroll
+      for (int r_ = 0; r_ < 3; ++r_) {
+        const int i = g + 4 * r_;
+        if (c < 12) sGM[i * 25 + c] = c == i ? G[r_] + (Dk[i] != 0.0 ? Dk[i] : 1.0) : G[r_];
+        sGM[i * 25 + 12 + c] = M[r_];
+      }
+    }
+    __syncthreads();
+    // eliminate, one column per lane (lanes past 24 repeat column 24), then back-substitute the
+    // 13 right-hand sides on lanes 12..24, column by column: once y[j] is known every row
+    // above takes its term, so the dependent chain is two operations per unknown
+    {
+      const int cc = min(lane, 24);
+      double col[12], rp[12], y[12];
+#pragma unroll
+      for (int i = 0; i < 12; ++i) col[i] = sGM[i * 25 + cc];
+#pragma unroll
+      for (int j = 0; j < 12; ++j) {
+        rp[j] = gain_rcp(gain_bcast(col[j], j));
+#pragma unroll
+        for (int i = j + 1; i < 12; ++i) {
+          const double mij = gain_bcast(col[i], j) * rp[j];
+          col[i] = fma(-mij, col[j], col[i]);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 12; ++i) y[i] = col[i];
+#pragma unroll
+      for (int j = 11; j >= 0; --j) {
+        y[j] *= rp[j];
+#pragma unroll
+        for (int i = 0; i < j; ++i) y[i] = fma(-gain_bcast(col[i], j), y[j], y[i]);
+      }
+      if (lane >= 12 && lane < 25) {
+#pragma unroll
+        for (int i = 0; i < 12; ++i) sY[i * 13 + lane - 12] = -y[i];
+      }
+    }
+    __syncthreads();
+    // [K_k | kappa_k] = Z [Kp | kp] + [0 | c_k] as a B operand; kept in LDS for the outputs
+    double kb[3], ka[3], kpb[3];
+    const int c13 = min(c, 12);
+#pragma unroll
+    for (int q_ = 0; q_ < 3; ++q_) {
+      const int rq = 4 * q_ + g, leg = rq / 3, ax = rq - 3 * leg;
+      const double yv = sY[rq * 13 + c13];
+      double v = yv;
+      if (ax < 2)
+        v = fma((double)(ax == 0 ? sZx[k * 4 + leg] : sZy[k * 4 + leg]),
+                sY[(3 * leg + 2) * 13 + c13], v);
+      if (c == 12) v += sCv[k * 12 + rq];
+      kb[q_] = c < 13 ? v : 0.0;
+      kpb[q_] = c < 13 ? yv : 0.0;
+      ka[q_] = c < 12 ? yv * Dk[rq] : 0.0;
+      if (c < 12) Kk[rq * 12 + c] = v;
+      else if (c == 12) Kk[144 + rq] = v;
+    }
+    const gain_d4 ad0 = {adg[0], adg[1], adg[2], 0.0};
+    gain_d4 AC = gain_mm(ab, kb, ad0);  // [A_cl | d_cl] = [Ad | gd] + Bd_k [K_k | kappa_k]
+    double acb[3], sacb[3];
+#pragma unroll
+    for (int r_ = 0; r_ < 3; ++r_) acb[r_] = AC[r_];
+    gain_d4 SAC = gain_mm(sa, acb, zero);  // [S A_cl | S d_cl]
+#pragma unroll
+    for (int r_ = 0; r_ < 3; ++r_) sacb[r_] = c == 12 ? SAC[r_] + sreg[r_] : SAC[r_];
+    gain_d4 Pn = gain_mm(acb, sacb, zero);  // [A_cl'S A_cl | A_cl'(S d_cl + s)]
+    Pn = gain_mm(ka, kpb, Pn);              // + [Kp'D Kp | Kp'D kp]
+#pragma unroll
+    for (int r_ = 0; r_ < 3; ++r_) {
+      if (c < 12) sP[(g + 4 * r_) * 12 + c] = Pn[r_];
+      qreg[r_] = Pn[r_];  // q_k on lanes c == 12
+    }
+    __syncthreads();
+  }
+}
+
 __global__ void __launch_bounds__(64) gain_kernel(GainArgs a, int64_t B, int keep_steps) {
   __shared__ ProblemLds sp;
   auto& [sBd, sAd, sXr, sGX, sQ, sR, sC] = sp;
@@ -183,128 +328,10 @@ __global__ void __launch_bounds__(64) gain_kernel(GainArgs a, int64_t B, int kee
     for (int e = lane; e < 144; e += 64) sP[e] = 0.0;
     __syncthreads();
 
-    // ---- backward Riccati recursion on the f64 matrix cores.  Lane (c, g) = (lane & 15,
-    // lane >> 4) holds, of a 12x12 matrix X padded to 16x16, the three entries X[4q + g][c]:
-    // that is the B operand of X (pass q carries k = 4q + g), the A operand of X', and the
-    // layout a product comes out in (row g + 4 reg, column c) -- so products chain from
-    // register to register.  Column 12 of the B side carries the affine part (d, s, kappa, q).
+    // ---- backward Riccati recursion on the f64 matrix cores (gain_recursion)
     const int c = lane & 15, g = lane >> 4;
-    const int cl = min(c, 11), cleg = cl / 3, cax = cl - 3 * cleg;
-    double adg[3], qreg[3] = {0.0, 0.0, 0.0};  // [Ad | gd] in that layout; q_{k+1} on lanes c == 12
-#pragma unroll
-    for (int q_ = 0; q_ < 3; ++q_) {
-      const int rq = 4 * q_ + g;
-      adg[q_] = c < 12 ? (double)sAd[rq * 12 + c] : (c == 12 ? (double)sGX[rq] : 0.0);
-    }
-    for (int k = N - 1; k >= 0; --k) {
-      const float* const Bk = sBd + k * 144;
-      const double* const Dk = sD + k * 12;
-      double* const Kk = sK + (keep_steps ? k : 0) * kGainSlot;
-      const bool used = c < 12 && Dk[cl] != 0.0;
-      double sa[3], bt[3], wv[3], ab[3], sreg[3];
-#pragma unroll
-      for (int q_ = 0; q_ < 3; ++q_) {
-        const int rq = 4 * q_ + g;
-        // S = Q + P_{k+1}, mirrored here: A operand S[c][rq]
-        const double sym = 0.5 * (sP[cl * 12 + rq] + sP[rq * 12 + cl]) + (cl == rq ? sQ[cl] : 0.0);
-        sa[q_] = c < 12 ? sym : 0.0;
-        // Bt = Bd_k Z: column c is slot c of leg cleg
-        const float* const bi = Bk + rq * 12 + 3 * cleg;
-        const double v = cax == 2 ? fma((double)sZx[k * 4 + cleg], (double)bi[0],
-                                        fma((double)sZy[k * 4 + cleg], (double)bi[1], (double)bi[2]))
-                                  : (double)bi[cax];
-        bt[q_] = used ? v : 0.0;
-        wv[q_] = c == 12 ? sDv[k * 12 + rq] : adg[q_];  // [Ad | d_k], 0 past column 12
-        ab[q_] = c < 12 ? (double)Bk[cl * 12 + rq] : 0.0;  // A operand Bd_k[c][rq]
-        sreg[q_] = qreg[q_] - sQ[rq] * (double)sXr[k * 12 + rq];  // s, used on lanes c == 12
-      }
-      const gain_d4 zero = {0.0, 0.0, 0.0, 0.0};
-      gain_d4 SW = gain_mm(sa, wv, zero);  // [S Ad | S d]
-      gain_d4 SB = gain_mm(sa, bt, zero);  // S Bt
-      double swb[3], sbb[3];
-#pragma unroll
-      for (int r_ = 0; r_ < 3; ++r_) {
-        swb[r_] = c == 12 ? SW[r_] + sreg[r_] : SW[r_];  // column 12: S d + s
-        sbb[r_] = SB[r_];
-      }
-      gain_d4 G = gain_mm(bt, sbb, zero);  // Bt'S Bt
-      gain_d4 M = gain_mm(bt, swb, zero);  // [Bt'S Ad | Bt'(S d + s)]
-      // [G | M] to LDS, G = Bt'S Bt + D with 1 on the diagonal of a slot not in use
-      if (c < 13) {
-#pragma unroll
-        for (int r_ = 0; r_ < 3; ++r_) {
-          const int i = g + 4 * r_;
-          if (c < 12) sGM[i * 25 + c] = c == i ? G[r_] + (Dk[i] != 0.0 ? Dk[i] : 1.0) : G[r_];
-          sGM[i * 25 + 12 + c] = M[r_];
-        }
-      }
-      __syncthreads();
-      // eliminate, one column per lane (lanes past 24 repeat column 24), then back-substitute the
-      // 13 right-hand sides on lanes 12..24, column by column: once y[j] is known every row
-      // above takes its term, so the dependent chain is two operations per unknown
-      {
-        const int cc = min(lane, 24);
-        double col[12], rp[12], y[12];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) col[i] = sGM[i * 25 + cc];
-#pragma unroll
-        for (int j = 0; j < 12; ++j) {
-          rp[j] = gain_rcp(gain_bcast(col[j], j));
-#pragma unroll
-          for (int i = j + 1; i < 12; ++i) {
-            const double mij = gain_bcast(col[i], j) * rp[j];
-            col[i] = fma(-mij, col[j], col[i]);
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < 12; ++i) y[i] = col[i];
-#pragma unroll
-        for (int j = 11; j >= 0; --j) {
-          y[j] *= rp[j];
-#pragma unroll
-          for (int i = 0; i < j; ++i) y[i] = fma(-gain_bcast(col[i], j), y[j], y[i]);
-        }
-        if (lane >= 12 && lane < 25) {
-#pragma unroll
-          for (int i = 0; i < 12; ++i) sY[i * 13 + lane - 12] = -y[i];
-        }
-      }
-      __syncthreads();
-      // [K_k | kappa_k] = Z [Kp | kp] + [0 | c_k] as a B operand; kept in LDS for the outputs
-      double kb[3], ka[3], kpb[3];
-      const int c13 = min(c, 12);
-#pragma unroll
-      for (int q_ = 0; q_ < 3; ++q_) {
-        const int rq = 4 * q_ + g, leg = rq / 3, ax = rq - 3 * leg;
-        const double yv = sY[rq * 13 + c13];
-        double v = yv;
-        if (ax < 2)
-          v = fma((double)(ax == 0 ? sZx[k * 4 + leg] : sZy[k * 4 + leg]),
-                  sY[(3 * leg + 2) * 13 + c13], v);
-        if (c == 12) v += sCv[k * 12 + rq];
-        kb[q_] = c < 13 ? v : 0.0;
-        kpb[q_] = c < 13 ? yv : 0.0;
-        ka[q_] = c < 12 ? yv * Dk[rq] : 0.0;
-        if (c < 12) Kk[rq * 12 + c] = v;
-        else if (c == 12) Kk[144 + rq] = v;
-      }
-      const gain_d4 ad0 = {adg[0], adg[1], adg[2], 0.0};
-      gain_d4 AC = gain_mm(ab, kb, ad0);  // [A_cl | d_cl] = [Ad | gd] + Bd_k [K_k | kappa_k]
-      double acb[3], sacb[3];
-#pragma unroll
-      for (int r_ = 0; r_ < 3; ++r_) acb[r_] = AC[r_];
-      gain_d4 SAC = gain_mm(sa, acb, zero);  // [S A_cl | S d_cl]
-#pragma unroll
-      for (int r_ = 0; r_ < 3; ++r_) sacb[r_] = c == 12 ? SAC[r_] + sreg[r_] : SAC[r_];
-      gain_d4 Pn = gain_mm(acb, sacb, zero);  // [A_cl'S A_cl | A_cl'(S d_cl + s)]
-      Pn = gain_mm(ka, kpb, Pn);              // + [Kp'D Kp | Kp'D kp]
-#pragma unroll
-      for (int r_ = 0; r_ < 3; ++r_) {
-        if (c < 12) sP[(g + 4 * r_) * 12 + c] = Pn[r_];
-        qreg[r_] = Pn[r_];  // q_k on lanes c == 12
-      }
-      __syncthreads();
-    }
+    double qreg[3];
+    gain_recursion(sp, GainLds{sZx, sZy, sCv, sD, sDv, sP, sGM, sY, sK}, N, keep_steps, lane, qreg);
     if (c == 12) {
 #pragma unroll
       for (int r_ = 0; r_ < 3; ++r_) sq[g + 4 * r_] = qreg[r_];

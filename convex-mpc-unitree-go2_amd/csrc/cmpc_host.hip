@@ -22,6 +22,7 @@
 #include "cmpc_kkt.hip"       // cost and KKT residuals of a batch of points
 #include "cmpc_gain.hip"      // feedback gain and value function on the held faces
 #include "cmpc_vjp.hip"       // gradients of a loss through the optimum on the held faces
+#include "cmpc_refine.hip"    // certified float64 refinement around the optimum on the held faces
 
 constexpr int kNumGroups = 3;  // solve kernels (register classes), see solve_group_kernel
 static_assert(kNumGroups == CMPC_NUM_SOLVE_KERNELS, "one timing slot per solve kernel");
@@ -133,7 +134,7 @@ int io_copy(const IO* io, size_t min_size, const char* what, const char* type, I
   return CMPC_OK;
 }
 
-// The checks of an evaluation entry (cmpc_kkt_io, cmpc_gain_io, cmpc_vjp_io) after io_copy: plan, B, the six
+// The checks of an evaluation entry (cmpc_kkt_io, cmpc_gain_io, cmpc_vjp_io, cmpc_refine_io) after io_copy: plan, B, the six
 // problem arrays, face_tol, the device.  `own`: the entry's own required arrays are there;
 // `between`: the message of a failed check of the entry's own that ranks after the arrays, or NULL.
 template <class IO>
@@ -488,6 +489,33 @@ int cmpc_vjp_run(cmpc_plan* pl, int64_t B, const cmpc_vjp_io* io, void* stream) 
                      (hipStream_t)stream, k, B);  // one wave per instance
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "vjp_kernel launch");
+  return CMPC_OK;
+}
+
+int cmpc_refine_run(cmpc_plan* pl, int64_t B, const cmpc_refine_io* io, void* stream) {
+  cmpc_refine_io a;
+  if (int rc = io_copy(io, offsetof(cmpc_refine_io, info) + sizeof(io->info), "cmpc_refine_run",
+                       "cmpc_refine_io", a))
+    return rc;
+  const auto tol_ok = [](float t) { return t >= 0.f && std::isfinite(t); };
+  if (int rc = check_problem(
+          pl, B, a, a.info, "cmpc_refine_run",
+          !(a.w || a.faces) ? ": w and faces are both null (one must name the held faces)"
+          : a.max_rounds < 0 || a.max_rounds > CMPC_REFINE_MAX_ROUNDS
+              ? ": max_rounds must be in 0..16"
+          : !tol_ok(a.prim_tol) || !tol_ok(a.dual_tol)
+              ? ": prim_tol and dual_tol must be finite and >= 0"
+              : nullptr))
+    return rc;
+  const cmpc::RefineArgs k{problem_args(pl, a), a.w, a.faces, a.max_rounds,
+                           a.prim_tol > 0.f ? (double)a.prim_tol : 1e-9,
+                           a.dual_tol > 0.f ? (double)a.dual_tol : 1e-9,
+                           a.info, a.res, a.w64, a.lam_out, a.faces_out, a.w_out, a.status};
+  const size_t dyn = (size_t)k.p.N * cmpc::kGainSlot * sizeof(double);  // every step's (K_k, kappa_k)
+  hipLaunchKernelGGL(cmpc::refine_kernel, dim3(grid_stride_blocks(B)), dim3(64), dyn,
+                     (hipStream_t)stream, k, B);  // one wave per instance
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "refine_kernel launch");
   return CMPC_OK;
 }
 

@@ -1,5 +1,5 @@
 // cmpc_problem.h -- what the evaluation kernels next to the solver (cmpc_kkt.hip, cmpc_gain.hip,
-// cmpc_vjp.hip) share: the problem part of their argument blocks, its image in LDS, the staging of an instance
+// cmpc_vjp.hip, cmpc_refine.hip) share: the problem part of their argument blocks, its image in LDS, the staging of an instance
 // into it, the instance's constants with the validity decision, and the face rule.
 // Included by those files only; the solve kernels have their own inputs and an fp32 face
 // rule with a slack (cmpc_device.h, cmpc_wave.hip).

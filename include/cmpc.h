@@ -395,6 +395,97 @@ typedef struct cmpc_vjp_io {
 } cmpc_vjp_io;
 int cmpc_vjp_run(cmpc_plan* plan, int64_t B, const cmpc_vjp_io* io, void* stream);
 
+/* Certified float64 refinement of B solved instances, on the device: a primal-dual active-set
+ * loop around cmpc_gain_io's u_star that replaces an answer only when the float64 KKT conditions
+ * hold on the whole QP, and reports how far the answer given was from that optimum.
+ * Per instance the masks of the held faces are read from `faces` or off w's forces, as
+ * cmpc_gain_run does.  Then, for round r = 0, 1, ..:
+ *   1. (u, x) = the optimum on the held faces and its float64 rollout (cmpc_gain_io's u_star)
+ *   2. the costate pass  p_k = 2Q (x_{k+1} - xref_k) + Ad' p_{k+1},  p_N = 0,  and
+ *      g_k = 2R u_k + Bd_k' p_k
+ *   3. per stance leg, with (gx, gy, gz) its part of g_k: a held sx mu face of x (sx = +-1) has
+ *      the multiplier lam_x = -sx gx, the same for y, a face not held 0, and a held fz face
+ *      lam_z = gz - mu (lam_x + lam_y)
+ *   4. with us = max(1, max|u|) and gs = us x min_i 2R_i, a face not held is violated when its
+ *      row  fx - mu fz, -fx - mu fz, fy - mu fz, -fy - mu fz  or  fz_min - fz  is above
+ *      prim_tol x us (where both signs of an axis are, only the larger row counts, the + face on
+ *      a tie), and a held face is negative when its multiplier is below -dual_tol x gs
+ *   5. neither violated nor negative: certified, stop.  r == max_rounds: stop.  Any face
+ *      violated: every violated face is added (adding one sign of an axis clears the other) and
+ *      nothing is dropped; otherwise every negative face is dropped.  The new masks equal those
+ *      of an earlier round of this instance: stop.
+ * Outputs, all of the last round's point:
+ *   info      [B]        int32  required.  r >= 0: certified after r repairs.
+ *                               CMPC_REFINE_INVALID: a mu / fz_min entry or Q / R row invalid by
+ *                               the rules of cmpc_solve_io, or a given mask that holds both signs
+ *                               of an axis (every inconsistent mask does).  The refinement never
+ *                               creates such a mask and does not certify an apex.
+ *                               CMPC_REFINE_ROUNDS: not certified within max_rounds repairs.
+ *                               CMPC_REFINE_CYCLE: a set of masks came back.
+ *                               A certified point satisfies every constraint within
+ *                               prim_tol x us and is the exact optimum on its faces, whose
+ *                               multipliers are above -dual_tol x gs.  The QP is strongly convex
+ *                               with modulus min_i 2R_i, so its forces are within
+ *                               |sum_f min(lam_f, 0) a_f|_2 / min_i 2R_i  (a_f the row of face f)
+ *                               of the QP's optimum: a few tens of dual_tol x us.
+ *   res       [B][3]     fp64   nullable.  [0] the largest row of a face not held, divided by
+ *                               us (0 when none is positive); [1] the most negative multiplier of
+ *                               a held face, divided by gs (0 when none is negative);
+ *                               [2] max|u - u_in| / max(1, max|u_in|), u_in the forces of w: on a
+ *                               certified instance, the measured error of the answer given.  NaN
+ *                               when w is NULL.
+ *   w64       [B][24N]   fp64   nullable; the point in w_out's layout: the states of the float64
+ *                               rollout, then the forces
+ *   lam_out   [B][52N]   fp64   nullable; the multipliers [lam_x | lam_a], layout and signs as
+ *                               cmpc_solve_ref's lam_out (and cmpc_kkt_run's recovery): lam_a =
+ *                               [-p_k | the four friction multipliers per (step, leg)],
+ *                               lam_x = -lam_z on a stance fz and -g on a swing force.  Negative
+ *                               face multipliers are written as they are.
+ *   faces_out [B][N][4]  uint8  nullable; the masks, 0 on a swing leg
+ *   w_out     [B][24N]   fp32   nullable; may be w.  Written only for a certified instance, as
+ *                               the fp32 rounding of w64; every other row is left untouched, bit
+ *                               for bit: the entry never makes an answer worse.
+ *   status    [B]        int32  nullable, in/out: set to 1 for a certified instance, untouched
+ *                               otherwise
+ * An invalid instance gets NaN in res, w64 and lam_out and 0xFF in faces_out; it never fails the
+ * call and the other instances are unaffected.
+ *   Ad..contact, mu, fz_min, Q, R, faces, face_tol   as in cmpc_gain_io.  w as there, and with
+ *                               faces given still the answer res[2] measures.  w and faces both
+ *                               NULL: CMPC_E_INVALID.
+ *   max_rounds                  the repair limit, 0..16; 0 checks only.  Out of range:
+ *                               CMPC_E_INVALID.
+ *   prim_tol, dual_tol          0 selects 1e-9.  Negative or not finite: CMPC_E_INVALID.
+ * `size` is the caller's sizeof of the struct (fields past it read as NULL or 0); it must reach
+ * past `info`.  B >= 1; no workspace is used, so the plan's max_batch does not limit B.  Each sum
+ * runs in a fixed order: the results are bitwise repeatable and do not depend on B or on the
+ * instance's place in the batch.  Same guarantees as cmpc_solve: asynchronous on `stream`, no
+ * allocation, no host synchronisation, graph-capturable; the plan's device must be current. */
+typedef struct cmpc_refine_io {
+  uint32_t size;            /* sizeof of this struct in the caller's header */
+  const float *Ad, *Bd, *gd, *x0, *xref;  /* as cmpc_solve */
+  const uint8_t* contact;
+  const float *mu, *fz_min; /* [B] nullable: the plan's constants */
+  const float *Q, *R;       /* [B][12] nullable */
+  const float* w;           /* [B][24N] nullable: the answer to refine */
+  const uint8_t* faces;     /* [B][N][4] nullable: held faces given by the caller */
+  float face_tol;           /* used when faces == NULL; 0 selects 1e-6 */
+  int32_t max_rounds;       /* 0..16 */
+  float prim_tol, dual_tol; /* 0 selects 1e-9 */
+  int32_t* info;            /* [B] out, required */
+  double* res;              /* [B][3] nullable */
+  double* w64;              /* [B][24N] nullable */
+  double* lam_out;          /* [B][52N] nullable */
+  uint8_t* faces_out;       /* [B][N][4] nullable */
+  float* w_out;             /* [B][24N] nullable, may be w */
+  int32_t* status;          /* [B] nullable, in/out */
+} cmpc_refine_io;
+
+#define CMPC_REFINE_INVALID (-1)
+#define CMPC_REFINE_ROUNDS (-2)
+#define CMPC_REFINE_CYCLE (-3)
+#define CMPC_REFINE_MAX_ROUNDS 16
+int cmpc_refine_run(cmpc_plan* plan, int64_t B, const cmpc_refine_io* io, void* stream);
+
 void cmpc_plan_destroy(cmpc_plan* plan);
 
 /* QP data on the device: the reference's discrete dynamics
