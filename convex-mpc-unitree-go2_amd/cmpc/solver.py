@@ -158,6 +158,29 @@ class Plan:
                 self._same_device(t)
                 setattr(io, name, t.data_ptr())
 
+    def _need(self, entry: str, method: str):
+        """An evaluation entry that a library built from older sources does not have."""
+        if not hasattr(self.lib, entry):
+            raise CmpcError(f"cmpc: this libcmpc.so has no {entry}: Plan.{method} needs a library "
+                            "built from sources that declare it")
+
+    def _results(self, io, spec: dict, want, always, out, device) -> dict:
+        """The results ``always`` + ``want`` of an evaluation entry, taken from ``out`` or
+        allocated on ``device`` and checked against spec's name -> (io field, dtype, shape), with
+        io's fields pointed at them: the dict the entry returns."""
+        out = dict(out or {})
+        res = {}
+        for name in tuple(always) + tuple(n for n in want if n not in always):
+            field, dtype, shape = spec[name]
+            t = out.get(name)
+            if t is None:
+                t = torch.empty(shape, dtype=dtype, device=device)
+            _dev_tensor(t, name, dtype, shape)
+            self._same_device(t)
+            setattr(io, field, t.data_ptr())
+            res[name] = t
+        return res
+
     def set_timing(self, enable: bool):
         _check(self.lib, self.lib.cmpc_plan_set_timing(self._h, int(bool(enable))),
                "cmpc_plan_set_timing")
@@ -369,9 +392,7 @@ class Plan:
         with an invalid mu / fz_min entry or Q / R row gets four NaNs.  Asynchronous on
         ``stream`` (default: torch's current stream), no allocation when ``out`` is given,
         graph-capturable; the inputs are not modified and B is not limited by max_batch."""
-        if not hasattr(self.lib, "cmpc_kkt_run"):
-            raise CmpcError("cmpc: this libcmpc.so has no cmpc_kkt_run: Plan.kkt needs a library "
-                            "built from sources that declare it")
+        self._need("cmpc_kkt_run", "kkt")
         N = self.params.N
         B = Ad.shape[0]
         if B < 1:
@@ -412,9 +433,7 @@ class Plan:
         the wanted names.  Asynchronous on ``stream`` (default: torch's current stream), no
         allocation when every wanted name is in ``out``, graph-capturable; the inputs are not
         modified and B is not limited by max_batch."""
-        if not hasattr(self.lib, "cmpc_gain_run"):
-            raise CmpcError("cmpc: this libcmpc.so has no cmpc_gain_run: Plan.gain needs a library "
-                            "built from sources that declare it")
+        self._need("cmpc_gain_run", "gain")
         want = tuple(want)
         unknown = [n for n in want if n not in _lib.GAIN_OUTPUTS]
         if unknown:
@@ -433,17 +452,7 @@ class Plan:
                            **_instance_spec(B, mu, fz_min, Q, R)))
         spec = dict(K=("K", f64, (B, 12, 12)), Vx=("Vx", f64, (B, 12)), Vxx=("Vxx", f64, (B, 12, 12)),
                     u_star=("u_star", f64, (B, 12 * N)), faces=("faces_out", u8, (B, N, 4)))
-        out = dict(out or {})
-        res = {}
-        for name in ("K",) + tuple(n for n in want if n != "K"):
-            field, dtype, shape = spec[name]
-            t = out.get(name)
-            if t is None:
-                t = torch.empty(shape, dtype=dtype, device=Ad.device)
-            _dev_tensor(t, name, dtype, shape)
-            self._same_device(t)
-            setattr(io, field, t.data_ptr())
-            res[name] = t
+        res = self._results(io, spec, want, ("K",), out, Ad.device)
         io.face_tol = 0.0 if face_tol is None else float(face_tol)
         sp = _stream_ptr(stream, Ad.device)
         with torch.cuda.device(Ad.device):
@@ -469,9 +478,7 @@ class Plan:
         or all of the wanted names.  Asynchronous on ``stream`` (default: torch's current
         stream), no allocation when every wanted name is in ``out``, graph-capturable; the
         inputs are not modified and B is not limited by max_batch."""
-        if not hasattr(self.lib, "cmpc_vjp_run"):
-            raise CmpcError("cmpc: this libcmpc.so has no cmpc_vjp_run: Plan.vjp needs a library "
-                            "built from sources that declare it")
+        self._need("cmpc_vjp_run", "vjp")
         want = tuple(want)
         unknown = [n for n in want if n not in _lib.VJP_OUTPUTS]
         if unknown or not want:
@@ -491,16 +498,8 @@ class Plan:
                            **_instance_spec(B, mu, fz_min, Q, R)))
         shapes = dict(x0=(B, 12), xref=(B, N, 12), gd=(B, 12), Q=(B, 12), R=(B, 12), mu=(B,),
                       fz_min=(B,), Ad=(B, 12, 12), Bd=(B, N, 12, 12))
-        out = dict(out or {})
-        res = {}
-        for name in want:
-            t = out.get(name)
-            if t is None:
-                t = torch.empty(shapes[name], dtype=f64, device=Ad.device)
-            _dev_tensor(t, name, f64, shapes[name])
-            self._same_device(t)
-            setattr(io, "g_" + name, t.data_ptr())
-            res[name] = t
+        spec = {name: ("g_" + name, f64, shape) for name, shape in shapes.items()}
+        res = self._results(io, spec, want, (), out, Ad.device)
         io.face_tol = 0.0 if face_tol is None else float(face_tol)
         sp = _stream_ptr(stream, Ad.device)
         with torch.cuda.device(Ad.device):
@@ -535,9 +534,7 @@ class Plan:
         ``faces``).  ``out`` is a dict of preallocated tensors for some or all of the wanted
         names.  Asynchronous on ``stream`` (default: torch's current stream), no allocation when
         every wanted name is in ``out``, graph-capturable; B is not limited by max_batch."""
-        if not hasattr(self.lib, "cmpc_refine_run"):
-            raise CmpcError("cmpc: this libcmpc.so has no cmpc_refine_run: Plan.refine needs a "
-                            "library built from sources that declare it")
+        self._need("cmpc_refine_run", "refine")
         want = tuple(want)
         unknown = [n for n in want if n not in _lib.REFINE_OUTPUTS]
         if unknown:
@@ -558,17 +555,7 @@ class Plan:
         spec = dict(info=("info", i32, (B,)), res=("res", f64, (B, 3)),
                     w64=("w64", f64, (B, 24 * N)), lam=("lam_out", f64, (B, 52 * N)),
                     faces=("faces_out", u8, (B, N, 4)))
-        out = dict(out or {})
-        res = {}
-        for name in ("info",) + tuple(n for n in want if n != "info"):
-            field, dtype, shape = spec[name]
-            t = out.get(name)
-            if t is None:
-                t = torch.empty(shape, dtype=dtype, device=Ad.device)
-            _dev_tensor(t, name, dtype, shape)
-            self._same_device(t)
-            setattr(io, field, t.data_ptr())
-            res[name] = t
+        res = self._results(io, spec, want, ("info",), out, Ad.device)
         io.face_tol = float(face_tol)
         io.max_rounds = int(max_rounds)
         io.prim_tol, io.dual_tol = float(prim_tol), float(dual_tol)

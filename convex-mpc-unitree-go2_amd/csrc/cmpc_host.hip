@@ -169,9 +169,28 @@ cmpc::ProblemArgs problem_args(const cmpc_plan* pl, const IO& a) {
   return k;
 }
 
+// the held-face part of the argument blocks of cmpc_gain_run, cmpc_vjp_run and cmpc_refine_run:
+// given faces take the place of w's unless the kernel reads w for more than its faces (keep_w)
+template <class IO>
+cmpc::HeldArgs held_args(const cmpc_plan* pl, const IO& a, bool keep_w) {
+  return {problem_args(pl, a), a.faces && !keep_w ? nullptr : a.w, a.faces};
+}
+
+constexpr const char* kNoFaces = ": w and faces are both null (one must name the held faces)";
+
 // blocks of a grid-stride launch over B items
 unsigned grid_stride_blocks(int64_t B, int64_t cap = 8192) {
   return (unsigned)std::min(B, cap);
+}
+
+// launch an evaluation kernel, one wave per instance, grid-stride over B
+template <class K, class... A>
+int launch_eval(K kernel, const char* what, int64_t B, size_t dyn_lds, void* stream, A... args) {
+  hipLaunchKernelGGL(kernel, dim3(grid_stride_blocks(B)), dim3(64), dyn_lds, (hipStream_t)stream,
+                     args...);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, what);
+  return CMPC_OK;
 }
 
 }  // namespace
@@ -442,11 +461,7 @@ int cmpc_kkt_run(cmpc_plan* pl, int64_t B, const cmpc_kkt_io* io, void* stream) 
     return rc;
   if (int rc = check_problem(pl, B, a, a.w && a.res, "cmpc_kkt_run")) return rc;
   const cmpc::KktArgs k{problem_args(pl, a), a.w, a.lam, a.res};
-  hipLaunchKernelGGL(cmpc::kkt_kernel, dim3(grid_stride_blocks(B)), dim3(64), 0,
-                     (hipStream_t)stream, k, B);  // one wave per instance
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "kkt_kernel launch");
-  return CMPC_OK;
+  return launch_eval(cmpc::kkt_kernel, "kkt_kernel launch", B, 0, stream, k, B);
 }
 
 int cmpc_gain_run(cmpc_plan* pl, int64_t B, const cmpc_gain_io* io, void* stream) {
@@ -454,20 +469,13 @@ int cmpc_gain_run(cmpc_plan* pl, int64_t B, const cmpc_gain_io* io, void* stream
   if (int rc = io_copy(io, offsetof(cmpc_gain_io, K) + sizeof(io->K), "cmpc_gain_run",
                        "cmpc_gain_io", a))
     return rc;
-  if (int rc = check_problem(pl, B, a, a.K, "cmpc_gain_run",
-                             a.w || a.faces ? nullptr : ": w and faces are both null (one must "
-                                                        "name the held faces)"))
+  if (int rc = check_problem(pl, B, a, a.K, "cmpc_gain_run", a.w || a.faces ? nullptr : kNoFaces))
     return rc;
-  const cmpc::GainArgs k{problem_args(pl, a), a.faces ? nullptr : a.w, a.faces, a.K, a.Vx, a.Vxx,
-                         a.u_star, a.faces_out};
+  const cmpc::GainArgs k{held_args(pl, a, false), a.K, a.Vx, a.Vxx, a.u_star, a.faces_out};
   // the forward pass needs every step's (K_k, kappa_k) in LDS; K alone keeps one slot
   const int keep = a.u_star ? 1 : 0;
   const size_t dyn = (size_t)(keep ? k.p.N : 1) * cmpc::kGainSlot * sizeof(double);
-  hipLaunchKernelGGL(cmpc::gain_kernel, dim3(grid_stride_blocks(B)), dim3(64), dyn,
-                     (hipStream_t)stream, k, B, keep);  // one wave per instance
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "gain_kernel launch");
-  return CMPC_OK;
+  return launch_eval(cmpc::gain_kernel, "gain_kernel launch", B, dyn, stream, k, B, keep);
 }
 
 int cmpc_vjp_run(cmpc_plan* pl, int64_t B, const cmpc_vjp_io* io, void* stream) {
@@ -478,18 +486,13 @@ int cmpc_vjp_run(cmpc_plan* pl, int64_t B, const cmpc_vjp_io* io, void* stream) 
   const bool any = a.g_x0 || a.g_xref || a.g_gd || a.g_Q || a.g_R || a.g_mu || a.g_fz_min ||
                    a.g_Ad || a.g_Bd;
   if (int rc = check_problem(pl, B, a, a.gw, "cmpc_vjp_run",
-                             !(a.w || a.faces) ? ": w and faces are both null (one must name the "
-                                                 "held faces)"
+                             !(a.w || a.faces) ? kNoFaces
                              : !any ? ": every output is null (one must be given)" : nullptr))
     return rc;
-  const cmpc::VjpArgs k{problem_args(pl, a), a.faces ? nullptr : a.w, a.faces, a.gw, a.g_x0,
-                        a.g_xref, a.g_gd, a.g_Q, a.g_R, a.g_mu, a.g_fz_min, a.g_Ad, a.g_Bd};
+  const cmpc::VjpArgs k{held_args(pl, a, false), a.gw, a.g_x0, a.g_xref, a.g_gd, a.g_Q, a.g_R,
+                        a.g_mu, a.g_fz_min, a.g_Ad, a.g_Bd};
   const size_t dyn = (size_t)k.p.N * cmpc::kVjpSlot * sizeof(double);
-  hipLaunchKernelGGL(cmpc::vjp_kernel, dim3(grid_stride_blocks(B)), dim3(64), dyn,
-                     (hipStream_t)stream, k, B);  // one wave per instance
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "vjp_kernel launch");
-  return CMPC_OK;
+  return launch_eval(cmpc::vjp_kernel, "vjp_kernel launch", B, dyn, stream, k, B);
 }
 
 int cmpc_refine_run(cmpc_plan* pl, int64_t B, const cmpc_refine_io* io, void* stream) {
@@ -500,23 +503,19 @@ int cmpc_refine_run(cmpc_plan* pl, int64_t B, const cmpc_refine_io* io, void* st
   const auto tol_ok = [](float t) { return t >= 0.f && std::isfinite(t); };
   if (int rc = check_problem(
           pl, B, a, a.info, "cmpc_refine_run",
-          !(a.w || a.faces) ? ": w and faces are both null (one must name the held faces)"
+          !(a.w || a.faces) ? kNoFaces
           : a.max_rounds < 0 || a.max_rounds > CMPC_REFINE_MAX_ROUNDS
               ? ": max_rounds must be in 0..16"
           : !tol_ok(a.prim_tol) || !tol_ok(a.dual_tol)
               ? ": prim_tol and dual_tol must be finite and >= 0"
               : nullptr))
     return rc;
-  const cmpc::RefineArgs k{problem_args(pl, a), a.w, a.faces, a.max_rounds,
+  const cmpc::RefineArgs k{held_args(pl, a, true), a.max_rounds,
                            a.prim_tol > 0.f ? (double)a.prim_tol : 1e-9,
                            a.dual_tol > 0.f ? (double)a.dual_tol : 1e-9,
                            a.info, a.res, a.w64, a.lam_out, a.faces_out, a.w_out, a.status};
   const size_t dyn = (size_t)k.p.N * cmpc::kGainSlot * sizeof(double);  // every step's (K_k, kappa_k)
-  hipLaunchKernelGGL(cmpc::refine_kernel, dim3(grid_stride_blocks(B)), dim3(64), dyn,
-                     (hipStream_t)stream, k, B);  // one wave per instance
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "refine_kernel launch");
-  return CMPC_OK;
+  return launch_eval(cmpc::refine_kernel, "refine_kernel launch", B, dyn, stream, k, B);
 }
 
 // The event pair around one solve-kernel launch (cmpc_plan_timing_read).  timing_begin takes a

@@ -1,8 +1,9 @@
 // cmpc_problem.h -- what the evaluation kernels next to the solver (cmpc_kkt.hip, cmpc_gain.hip,
 // cmpc_vjp.hip, cmpc_refine.hip) share: the problem part of their argument blocks, its image in LDS, the staging of an instance
 // into it, the instance's constants with the validity decision, and the face rule.
-// Included by those files only; the solve kernels have their own inputs and an fp32 face
-// rule with a slack (cmpc_device.h, cmpc_wave.hip).
+// Included by cmpc_kkt.hip and, through cmpc_lq.h (what the last three share beyond this), by the
+// other three only; the solve kernels have their own inputs and an fp32 face rule with a slack
+// (cmpc_device.h, cmpc_wave.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,7 +12,7 @@
 
 namespace cmpc {
 
-// the leading fields of KktArgs, GainArgs and VjpArgs
+// the leading fields of KktArgs and of HeldArgs (cmpc_lq.h: GainArgs, VjpArgs, RefineArgs)
 struct ProblemArgs {
   int N;
   float Q2[12], R2[12];  // the plan's constants: 2Q, 2R

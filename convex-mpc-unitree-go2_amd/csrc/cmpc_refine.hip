@@ -4,8 +4,8 @@
 //
 // Per instance the masks of the held faces are read from `faces` or off w's forces (face_rule),
 // as gain_kernel does.  Then, round r = 0, 1, ..:
-//   1. (u, x): the optimum on the held faces and its rollout -- gain_recursion and gain_kernel's
-//      forward pass
+//   1. (u, x): the optimum on the held faces and its rollout -- gain_recursion<1> and
+//      gain_rollout<false>
 //   2. costate  p_k = 2Q (x_{k+1} - xref_k) + Ad' p_{k+1},  p_N = 0;   g_k = 2R u_k + Bd_k' p_k
 //   3. per stance leg, (gx, gy, gz) its part of g_k: a held sx mu face of x has
 //      lam_x = -sx gx (the same for y), a face not held 0, a held fz face
@@ -28,16 +28,14 @@
 // no atomics, no workspace.  w_out may be w: an instance's forces are staged before its row is
 // written, by the same wave.
 //
-// This file is compiled as part of cmpc_host.hip (single translation unit), after cmpc_gain.hip,
-// whose device helpers (gain_leg_set, gain_recursion) it uses as they are.
-#include "cmpc_problem.h"
+// This file is compiled as part of cmpc_host.hip (single translation unit).  The staging of the
+// held faces, the mask and its affine set, the recursion and the forward pass are cmpc_lq.h's, as
+// they are in cmpc_gain.hip and cmpc_vjp.hip.
+#include "cmpc_lq.h"
 
 namespace cmpc {
 
-struct RefineArgs {
-  ProblemArgs p;
-  const float* w;        // nullable: the input answer (its forces' faces when faces == NULL)
-  const uint8_t* faces;  // nullable
+struct RefineArgs : HeldArgs {  // w: the input answer too (its forces' faces when faces == NULL)
   int max_rounds;
   double prim_tol, dual_tol;
   int32_t* info;
@@ -87,16 +85,15 @@ __global__ void __launch_bounds__(64) refine_kernel(RefineArgs a, int64_t B) {
   const int lane = threadIdx.x;
   const int N = a.p.N;
   const double nan = __builtin_nan("");
+  const GainLds s{sZx, sZy, sCv, sD, sDv, sP, sGM, sY, sK};
 
   for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
     // ---- stage the instance as gain_kernel does: the problem's loads, the given faces and the
-    // forces of w, all issued before the first LDS write waits for one
+    // forces of w (held_issue), all issued before the first LDS write waits for one
     const ProblemLoads ld = problem_issue(a.p, b, lane);
-    const uint8_t fgiven = (a.faces ? a.faces : a.p.contact)[b * N * 4 + ld.eC];
-    const float4 vU = (a.w ? reinterpret_cast<const float4*>(a.w + b * N * 24 + 12 * N)
-                           : reinterpret_cast<const float4*>(a.p.xref + b * N * 12))[ld.eX];
+    const HeldLoads hl = held_issue(a, ld, b);
     problem_commit(sp, ld);
-    reinterpret_cast<float4*>(sUin)[ld.eX] = vU;
+    reinterpret_cast<float4*>(sUin)[ld.eX] = hl.vU;
     const ProblemConsts pc = problem_consts(a.p, sp, ld);
     const double mu = pc.mu, fz_min = pc.fz_min;
     __syncthreads();
@@ -106,10 +103,7 @@ __global__ void __launch_bounds__(64) refine_kernel(RefineArgs a, int64_t B) {
     const int k_ = lane >> 2, leg_ = lane & 3;
     const bool stance = lane < 4 * N && sC[leg_ * N + k_] != 0;
     unsigned mask = 0;
-    if (stance)
-      mask = a.faces ? (fgiven & 31u)
-                     : face_rule((double)sUin[k_ * 12 + 3 * leg_], (double)sUin[k_ * 12 + 3 * leg_ + 1],
-                                 (double)sUin[k_ * 12 + 3 * leg_ + 2], mu, fz_min, a.p.tol);
+    if (stance) mask = held_mask(a, hl, sUin, lane, pc);
     const bool apex = (mask & 6u) == 6u || (mask & 24u) == 24u;
     // an apex mask or an invalid entry: NaN in the fp64 outputs, 0xFF in faces_out, w_out and
     // status untouched; the same decision in every lane
@@ -132,59 +126,14 @@ __global__ void __launch_bounds__(64) refine_kernel(RefineArgs a, int64_t B) {
     int info;
     double lamf[4], lamz, vmax, lmin, us, gs;  // of the last round
     for (int r = 0;; ++r) {
-      // the affine set of the lane's mask (gain_kernel's mask stage)
+      // the affine set of the lane's mask (its verdict is the apex test above) and the affine
+      // terms, then 1. the optimum on the held faces and its rollout
       sHist[r][lane] = (uint8_t)mask;
-      if (lane < 4 * N) {
-        bool fr[3];
-        double zx, zy, c[3];
-        gain_leg_set(mask, mu, fz_min, fr, zx, zy, c);
-        if (!stance) fr[0] = fr[1] = fr[2] = false;  // f = 0: zx = zy = c = 0 already (mask 0)
-        const double rx = sR[3 * leg_], ry = sR[3 * leg_ + 1], rz = sR[3 * leg_ + 2];
-        sZx[lane] = (float)zx;
-        sZy[lane] = (float)zy;
-        sCv[lane * 3] = c[0];
-        sCv[lane * 3 + 1] = c[1];
-        sCv[lane * 3 + 2] = c[2];
-        sD[lane * 3] = fr[0] ? rx : 0.0;
-        sD[lane * 3 + 1] = fr[1] ? ry : 0.0;
-        sD[lane * 3 + 2] = fr[2] ? fma(zx * zx, rx, fma(zy * zy, ry, rz)) : 0.0;
-      }
-      __syncthreads();
-      for (int e = lane; e < 12 * N; e += 64) {  // d_k = Bd_k c_k + gd
-        const int k = e / 12, i = e - 12 * k;
-        double acc = (double)sGX[i];
-#pragma unroll
-        for (int m = 0; m < 12; ++m) acc = fma((double)sBd[e * 12 + m], sCv[k * 12 + m], acc);
-        sDv[e] = acc;
-      }
-      for (int e = lane; e < 144; e += 64) sP[e] = 0.0;
-      __syncthreads();
-
-      // 1. the optimum on the held faces and its rollout
-      double qreg[3];
-      gain_recursion(sp, GainLds{sZx, sZy, sCv, sD, sDv, sP, sGM, sY, sK}, N, 1, lane, qreg);
-      if (lane < 12) sX[lane] = (double)sGX[12 + lane];
-      __syncthreads();
-      for (int k = 0; k < N; ++k) {
-        const double* const Kk = sK + k * kGainSlot;
-        if (lane < 12) {
-          double acc = Kk[144 + lane];
-#pragma unroll
-          for (int m = 0; m < 12; ++m) acc = fma(Kk[lane * 12 + m], sX[k * 12 + m], acc);
-          sUu[k * 12 + lane] = acc;
-        }
-        __syncthreads();
-        if (lane < 12) {
-          double xn = (double)sGX[lane];
-#pragma unroll
-          for (int m = 0; m < 12; ++m) xn = fma((double)sAd[lane * 12 + m], sX[k * 12 + m], xn);
-#pragma unroll
-          for (int m = 0; m < 12; ++m)
-            xn = fma((double)sBd[(k * 12 + lane) * 12 + m], sUu[k * 12 + m], xn);
-          sX[(k + 1) * 12 + lane] = xn;
-        }
-        __syncthreads();
-      }
+      if (lane < 4 * N) gain_leg_fill(sp, s, lane, mask, stance, pc);
+      gain_affine(sp, s, N, lane);
+      double qreg[3];  // (q_0: not used)
+      gain_recursion<1>(sp, s, N, 1, lane, qreg);
+      gain_rollout<false>(sp, sK, GainTraj{sX, sUu, nullptr, nullptr}, N, lane);
 
       // 2. the costate pass, then g_k of every step
       if (lane < 12) sCo[N * 12 + lane] = 0.0;

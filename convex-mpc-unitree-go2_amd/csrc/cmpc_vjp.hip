@@ -27,21 +27,17 @@
 // runs in an order the code fixes: bitwise repeatable, independent of B, of the instance's place
 // in the batch and of which outputs are asked for.  Plain stores, no atomics, no workspace.
 //
-// This file is compiled as part of cmpc_host.hip (single translation unit), after cmpc_gain.hip,
-// whose device helpers (gain_leg_set, gain_mm, gain_bcast, gain_rcp) it uses as they are.
-#include "cmpc_problem.h"
+// This file is compiled as part of cmpc_host.hip (single translation unit).  The staging of the
+// held faces, the mask and its affine set, the recursion (gain_recursion<2>) and the forward pass
+// (gain_rollout<true>) are cmpc_lq.h's, as they are in cmpc_gain.hip and cmpc_refine.hip.
+#include "cmpc_lq.h"
 
 namespace cmpc {
 
-struct VjpArgs {
-  ProblemArgs p;
-  const float* w;        // nullable: its forces' faces by face_rule with p.tol
-  const uint8_t* faces;  // nullable
-  const float* gw;       // [B][24N]
+struct VjpArgs : HeldArgs {
+  const float* gw;  // [B][24N]
   double *g_x0, *g_xref, *g_gd, *g_Q, *g_R, *g_mu, *g_fz, *g_Ad, *g_Bd;  // all nullable
 };
-
-constexpr int kVjpSlot = 168;  // doubles of one (K_k, kappa_k, kappa'_k) slot in LDS
 
 __global__ void __launch_bounds__(64) vjp_kernel(VjpArgs a, int64_t B) {
   __shared__ ProblemLds sp;
@@ -69,50 +65,33 @@ __global__ void __launch_bounds__(64) vjp_kernel(VjpArgs a, int64_t B) {
   const int lane = threadIdx.x;
   const int N = a.p.N;
   const bool need_co = a.g_x0 || a.g_gd || a.g_Ad || a.g_Bd || a.g_mu || a.g_fz;
+  const GainLds s{sZx, sZy, sCv, sD, sDv, sP, sGM, sY, sK, sGw};
 
   for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
     // ---- stage the instance: the problem's loads, then the given faces, the forces (xref where
     // w is absent: read and dropped) and gw, all issued before the first LDS write waits for one
     const ProblemLoads ld = problem_issue(a.p, b, lane);
-    const uint8_t fgiven = (a.faces ? a.faces : a.p.contact)[b * N * 4 + ld.eC];
-    const float4 vU = (a.w ? reinterpret_cast<const float4*>(a.w + b * N * 24 + 12 * N)
-                           : reinterpret_cast<const float4*>(a.p.xref + b * N * 12))[ld.eX];
+    const HeldLoads hl = held_issue(a, ld, b);
     const int eW0 = min(lane, 6 * N - 1), eW1 = min(lane + 64, 6 * N - 1);
     const float4* const gG = reinterpret_cast<const float4*>(a.gw + b * N * 24);
     const float4 vW0 = gG[eW0], vW1 = gG[eW1];
     problem_commit(sp, ld);
-    reinterpret_cast<float4*>(sU)[ld.eX] = vU;
+    reinterpret_cast<float4*>(sU)[ld.eX] = hl.vU;
     reinterpret_cast<float4*>(sGw)[eW0] = vW0;
     reinterpret_cast<float4*>(sGw)[eW1] = vW1;
     const ProblemConsts pc = problem_consts(a.p, sp, ld);
-    const double mu = pc.mu, fz_min = pc.fz_min;
+    const double mu = pc.mu;
     __syncthreads();
     const float* const sGwU = sGw + 12 * N;
 
     // ---- one lane per (step, leg): the mask, then its affine set
     bool ok = true;
     if (lane < 4 * N) {
-      const int k = lane >> 2, leg = lane & 3;
-      const bool stance = sC[leg * N + k] != 0;
+      const bool stance = sC[(lane & 3) * N + (lane >> 2)] != 0;
       unsigned mask = 0;
-      if (stance)
-        mask = a.faces ? (fgiven & 31u)
-                       : face_rule((double)sU[k * 12 + 3 * leg], (double)sU[k * 12 + 3 * leg + 1],
-                                   (double)sU[k * 12 + 3 * leg + 2], mu, fz_min, a.p.tol);
-      bool fr[3];
-      double zx, zy, c[3];
-      ok = gain_leg_set(mask, mu, fz_min, fr, zx, zy, c);
-      if (!stance) fr[0] = fr[1] = fr[2] = false;  // f = 0: zx = zy = c = 0 already (mask 0)
-      const double rx = sR[3 * leg], ry = sR[3 * leg + 1], rz = sR[3 * leg + 2];
-      sZx[lane] = (float)zx;
-      sZy[lane] = (float)zy;
+      if (stance) mask = held_mask(a, hl, sU, lane, pc);
       sMask[lane] = (uint8_t)mask;
-      sCv[lane * 3] = c[0];
-      sCv[lane * 3 + 1] = c[1];
-      sCv[lane * 3 + 2] = c[2];
-      sD[lane * 3] = fr[0] ? rx : 0.0;
-      sD[lane * 3 + 1] = fr[1] ? ry : 0.0;
-      sD[lane * 3 + 2] = fr[2] ? fma(zx * zx, rx, fma(zy * zy, ry, rz)) : 0.0;
+      ok = gain_leg_fill(sp, s, lane, mask, stance, pc);
     }
     // an inconsistent mask or an invalid entry: NaN in every output; the same decision in every
     // lane
@@ -138,179 +117,13 @@ __global__ void __launch_bounds__(64) vjp_kernel(VjpArgs a, int64_t B) {
       continue;
     }
 
-    // d_k = Bd_k c_k + gd of every step, off the serial chain
-    __syncthreads();
-    for (int e = lane; e < 12 * N; e += 64) {
-      const int k = e / 12, i = e - 12 * k;
-      double acc = (double)sGX[i];
-#pragma unroll
-      for (int m = 0; m < 12; ++m) acc = fma((double)sBd[e * 12 + m], sCv[k * 12 + m], acc);
-      sDv[e] = acc;
-    }
-    for (int e = lane; e < 144; e += 64) sP[e] = 0.0;
-    __syncthreads();
-
-    // ---- backward Riccati recursion on the f64 matrix cores, in gain_kernel's layout: lane
-    // (c, g) = (lane & 15, lane >> 4) holds X[4q + g][c] of a 12x12 matrix padded to 16x16.
-    // Column 12 of the B side carries the primal affine part (d, s, kappa, q), column 13 the
-    // adjoint's (0, s', kappa', q').
-    const int c = lane & 15, g = lane >> 4;
-    const int cl = min(c, 11), cleg = cl / 3, cax = cl - 3 * cleg;
-    double adg[3], qreg[3] = {0.0, 0.0, 0.0};  // [Ad | gd | 0]; q_{k+1}, q'_{k+1} on lanes c == 12, 13
-#pragma unroll
-    for (int q_ = 0; q_ < 3; ++q_) {
-      const int rq = 4 * q_ + g;
-      adg[q_] = c < 12 ? (double)sAd[rq * 12 + c] : (c == 12 ? (double)sGX[rq] : 0.0);
-    }
-    for (int k = N - 1; k >= 0; --k) {
-      const float* const Bk = sBd + k * 144;
-      const double* const Dk = sD + k * 12;
-      double* const Kk = sK + k * kVjpSlot;
-      const bool used = c < 12 && Dk[cl] != 0.0;
-      double sa[3], bt[3], wv[3], ab[3], sreg[3], rb[3];
-#pragma unroll
-      for (int q_ = 0; q_ < 3; ++q_) {
-        const int rq = 4 * q_ + g;
-        // S = Q + P_{k+1}, mirrored here: A operand S[c][rq]
-        const double sym = 0.5 * (sP[cl * 12 + rq] + sP[rq * 12 + cl]) + (cl == rq ? sQ[cl] : 0.0);
-        sa[q_] = c < 12 ? sym : 0.0;
-        // Bt = Bd_k Z: column c is slot c of leg cleg
-        const float* const bi = Bk + rq * 12 + 3 * cleg;
-        const double v = cax == 2 ? fma((double)sZx[k * 4 + cleg], (double)bi[0],
-                                        fma((double)sZy[k * 4 + cleg], (double)bi[1], (double)bi[2]))
-                                  : (double)bi[cax];
-        bt[q_] = used ? v : 0.0;
-        wv[q_] = c == 12 ? sDv[k * 12 + rq] : adg[q_];  // [Ad | d_k | 0], 0 past column 12
-        ab[q_] = c < 12 ? (double)Bk[cl * 12 + rq] : 0.0;  // A operand Bd_k[c][rq]
-        // s on lanes c == 12, s' on lanes c == 13
-        sreg[q_] = c == 13 ? fma(0.5, (double)sGw[k * 12 + rq], qreg[q_])
-                           : qreg[q_] - sQ[rq] * (double)sXr[k * 12 + rq];
-        rb[q_] = c == 13 ? 0.5 * (double)sGwU[k * 12 + rq] : 0.0;  // r = gw_u,k / 2 in column 13
-      }
-      const gain_d4 zero = {0.0, 0.0, 0.0, 0.0};
-      gain_d4 SW = gain_mm(sa, wv, zero);  // [S Ad | S d | 0]
-      gain_d4 SB = gain_mm(sa, bt, zero);  // S Bt
-      double swb[3], sbb[3];
-      const bool aff = c == 12 || c == 13;
-#pragma unroll
-      for (int r_ = 0; r_ < 3; ++r_) {
-        swb[r_] = aff ? SW[r_] + sreg[r_] : SW[r_];  // columns 12, 13: S d + s, s'
-        sbb[r_] = SB[r_];
-      }
-      gain_d4 G = gain_mm(bt, sbb, zero);  // Bt'S Bt
-      gain_d4 M = gain_mm(bt, swb, zero);  // [Bt'S Ad | Bt'(S d + s) | Bt's']
-      // [G | M] to LDS, G = Bt'S Bt + D with 1 on the diagonal of a slot not in use; column 13
-      // of M takes Z'r on the slots in use
-      if (c < 14) {
-#pragma unroll
-        for (int r_ = 0; r_ < 3; ++r_) {
-          const int i = g + 4 * r_, leg = i / 3, ax = i - 3 * leg;
-          if (c < 12) sGM[i * 26 + c] = c == i ? G[r_] + (Dk[i] != 0.0 ? Dk[i] : 1.0) : G[r_];
-          double m = M[r_];
-          if (c == 13 && Dk[i] != 0.0) {
-            const float* const ru = sGwU + k * 12 + 3 * leg;
-            const double zr = ax == 2 ? fma((double)sZx[k * 4 + leg], (double)ru[0],
-                                            fma((double)sZy[k * 4 + leg], (double)ru[1], (double)ru[2]))
-                                      : (double)ru[ax];
-            m = fma(0.5, zr, m);
-          }
-          sGM[i * 26 + 12 + c] = m;
-        }
-      }
-      __syncthreads();
-      // eliminate, one column per lane (lanes past 25 repeat column 25), then back-substitute the
-      // 14 right-hand sides on lanes 12..25, column by column
-      {
-        const int cc = min(lane, 25);
-        double col[12], rp[12], y[12];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) col[i] = sGM[i * 26 + cc];
-#pragma unroll
-        for (int j = 0; j < 12; ++j) {
-          rp[j] = gain_rcp(gain_bcast(col[j], j));
-#pragma unroll
-          for (int i = j + 1; i < 12; ++i) {
-            const double mij = gain_bcast(col[i], j) * rp[j];
-            col[i] = fma(-mij, col[j], col[i]);
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < 12; ++i) y[i] = col[i];
-#pragma unroll
-        for (int j = 11; j >= 0; --j) {
-          y[j] *= rp[j];
-#pragma unroll
-          for (int i = 0; i < j; ++i) y[i] = fma(-gain_bcast(col[i], j), y[j], y[i]);
-        }
-        if (lane >= 12 && lane < 26) {
-#pragma unroll
-          for (int i = 0; i < 12; ++i) sY[i * 14 + lane - 12] = -y[i];
-        }
-      }
-      __syncthreads();
-      // [K_k | kappa_k | kappa'_k] = Z [Kp | kp | kp'] + [0 | c_k | 0] as a B operand; kept in LDS
-      double kb[3], ka[3], kpb[3], kt[3];
-      const int c14 = min(c, 13);
-#pragma unroll
-      for (int q_ = 0; q_ < 3; ++q_) {
-        const int rq = 4 * q_ + g, leg = rq / 3, ax = rq - 3 * leg;
-        const double yv = sY[rq * 14 + c14];
-        double v = yv;
-        if (ax < 2)
-          v = fma((double)(ax == 0 ? sZx[k * 4 + leg] : sZy[k * 4 + leg]),
-                  sY[(3 * leg + 2) * 14 + c14], v);
-        if (c == 12) v += sCv[k * 12 + rq];
-        kb[q_] = c < 14 ? v : 0.0;
-        kpb[q_] = c < 14 ? yv : 0.0;
-        ka[q_] = c < 12 ? yv * Dk[rq] : 0.0;
-        kt[q_] = c < 12 ? v : 0.0;  // A operand K_k'
-        if (c < 12) Kk[rq * 12 + c] = v;
-        else if (c < 14) Kk[144 + 12 * (c - 12) + rq] = v;
-      }
-      const gain_d4 ad0 = {adg[0], adg[1], adg[2], 0.0};
-      gain_d4 AC = gain_mm(ab, kb, ad0);  // [A_cl | d_cl | d'_cl] = [Ad | gd | 0] + Bd_k [K_k | kappa_k | kappa'_k]
-      double acb[3], sacb[3];
-#pragma unroll
-      for (int r_ = 0; r_ < 3; ++r_) acb[r_] = AC[r_];
-      gain_d4 SAC = gain_mm(sa, acb, zero);  // [S A_cl | S d_cl | S d'_cl]
-#pragma unroll
-      for (int r_ = 0; r_ < 3; ++r_) sacb[r_] = aff ? SAC[r_] + sreg[r_] : SAC[r_];
-      gain_d4 Pn = gain_mm(acb, sacb, zero);  // [A_cl'S A_cl | A_cl'(S d_cl + s) | A_cl'(S d'_cl + s')]
-      Pn = gain_mm(ka, kpb, Pn);              // + [Kp'D Kp | Kp'D kp | Kp'D kp']
-      Pn = gain_mm(kt, rb, Pn);               // + [0 | 0 | K_k'r]
-#pragma unroll
-      for (int r_ = 0; r_ < 3; ++r_) {
-        if (c < 12) sP[(g + 4 * r_) * 12 + c] = Pn[r_];
-        qreg[r_] = Pn[r_];  // q_k, q'_k on lanes c == 12, 13
-      }
-      __syncthreads();
-    }
-
-    // ---- forward pass: lanes 0..11 the primal (x_k, u_k), lanes 32..43 the adjoint (dx_k, du_k)
+    // ---- the affine terms, then the backward Riccati recursion with the adjoint's column, then
+    // the forward pass: lanes 0..11 the primal (x_k, u_k), lanes 32..43 the adjoint (dx_k, du_k)
+    gain_affine(sp, s, N, lane);
+    double qreg[3];  // (q_0, q'_0: not used)
+    gain_recursion<2>(sp, s, N, 1, lane, qreg);
+    gain_rollout<true>(sp, sK, GainTraj{sX, sUu, sDX, sDU}, N, lane);
     const int half = lane >> 5, li = lane & 31, l12 = min(li, 11);
-    double* const tx = half ? sDX : sX;
-    double* const tu = half ? sDU : sUu;
-    if (li < 12) tx[li] = half ? 0.0 : (double)sGX[12 + li];
-    __syncthreads();
-    for (int k = 0; k < N; ++k) {
-      const double* const Kk = sK + k * kVjpSlot;
-      if (li < 12) {
-        double acc = Kk[144 + 12 * half + li];
-#pragma unroll
-        for (int m = 0; m < 12; ++m) acc = fma(Kk[li * 12 + m], tx[k * 12 + m], acc);
-        tu[k * 12 + li] = acc;
-      }
-      __syncthreads();
-      if (li < 12) {
-        double xn = half ? 0.0 : (double)sGX[li];
-#pragma unroll
-        for (int m = 0; m < 12; ++m) xn = fma((double)sAd[li * 12 + m], tx[k * 12 + m], xn);
-#pragma unroll
-        for (int m = 0; m < 12; ++m) xn = fma((double)sBd[(k * 12 + li) * 12 + m], tu[k * 12 + m], xn);
-        tx[(k + 1) * 12 + li] = xn;
-      }
-      __syncthreads();
-    }
 
     // ---- the outputs the trajectories give
     if (a.g_xref)

@@ -257,6 +257,32 @@ def test_arbitrary_single_sign_masks_and_invalid_entries(N):
     plan.close()
 
 
+@pytest.mark.parametrize("N", [1, 5, 16])
+def test_check_only_point_is_gains_u_star_bitwise(N):
+    """With the masks given and max_rounds = 0 the refinement's point is Plan.gain's u_star: both
+    run csrc/cmpc_lq.h's recursion and the same rollout arithmetic, so the forces agree byte for
+    byte on every row both evaluate, and the rows they decline coincide -- but for row 4, whose
+    both-signs mask without the fz face is consistent: gain evaluates it at fz = 0, the
+    refinement declines every apex."""
+    from cmpc import Plan, SolverParams
+    plan = Plan(SolverParams(N=N, max_batch=8))
+    c, faces, bad = _random_case(N)
+    idx = np.arange(64)
+    bad = [b for b in bad if b < 64]
+    r = _refine(plan, c, idx=idx, want=("w64",), use_w=False, faces=faces, max_rounds=0)["w64"][:, 12 * N:]
+    kw = {k: _dev(plan, c[k][idx]) for k in ("mu", "fz_min", "Q", "R")}
+    g = plan.gain(*[_dev(plan, c[k][idx]) for k in IN], faces=_dev(plan, faces[idx]),
+                  want=("u_star",), **kw)["u_star"].cpu().numpy()
+    fin_r, fin_g = np.isfinite(r).all(1), np.isfinite(g).all(1)
+    assert np.array_equal(np.flatnonzero(np.isnan(r).all(1)), bad) and np.all(fin_r[~np.isnan(r).all(1)])
+    assert np.array_equal(np.flatnonzero(np.isnan(g).all(1)), [b for b in bad if b != 4])
+    assert np.all(fin_g[~np.isnan(g).all(1)])
+    both = fin_r & fin_g
+    assert both.sum() == 64 - len(bad)
+    assert np.array_equal(r[both].view(np.uint64), g[both].view(np.uint64))
+    plan.close()
+
+
 def test_argument_checks(plan):
     """5. The CMPC_E_INVALID cases reach the caller as CmpcError (ValueError where the binding
     refuses first)."""

@@ -1,9 +1,9 @@
 """A/B of two library builds for bit-identical results: solve the headline batch (config 3,
 65,536) cold and its next tick warm, config 2 at 4,096 cold, and small batches that walk the
 paths those miss (small_cases), with the library given, and write (w, status, iterations, and
-y / lam where a case returns them, and what Plan.kkt and Plan.gain make of four of the small
-batches where the library has those entries); run once per library in separate processes, then
-compare.
+y / lam where a case returns them, and what Plan.kkt, Plan.gain, Plan.vjp and Plan.refine make of
+four of the small batches where the library has those entries: evaluate); run once per library
+in separate processes, then compare.
     python tools/bitwise_ab.py LIB OUT.npz            (GPU)
     python tools/bitwise_ab.py --compare A.npz B.npz   (CPU)"""
 import sys
@@ -43,8 +43,12 @@ def small_cases(res):
         return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
 
     def evaluate(tag, p, d, r, **kw):
-        """Plan.kkt with lam given and recovered, Plan.gain with every output, faces read off w
-        and then given, on the batch d solved with lam_out as r (kw: its per-robot values)."""
+        """On the batch d solved with lam_out as r (kw: its per-robot values): Plan.kkt with lam
+        given and recovered; Plan.gain with every output, faces read off w and then given;
+        Plan.vjp of a seeded gw the same two ways, and x0's gradient asked for alone (it must not
+        depend on what else is asked); Plan.refine with every output, w_out and status, faces
+        read off w, all-zero masks given next to w (no face held: the repair rounds run), and
+        max_rounds = 0."""
         out, w, lam = {}, r[0], r[3]
         if hasattr(p.lib, "cmpc_kkt_run"):
             out["kkt_given"] = p.kkt(*args(d), w, lam=lam, **kw)
@@ -54,6 +58,22 @@ def small_cases(res):
             out.update({f"gain_w_{k}": v for k, v in g.items()})
             g = p.gain(*args(d), faces=g["faces"], want=_lib.GAIN_OUTPUTS, **kw)
             out.update({f"gain_faces_{k}": v for k, v in g.items()})
+            held = g["faces"]
+        if hasattr(p.lib, "cmpc_vjp_run"):
+            gw = f32(np.random.default_rng(7).standard_normal(tuple(w.shape)))
+            for mode, sel in (("w", dict(w=w)), ("faces", dict(faces=held))):
+                g = p.vjp(*args(d), gw, want=_lib.VJP_OUTPUTS, **sel, **kw)
+                out.update({f"vjp_{mode}_{k}": v for k, v in g.items()})
+            out["vjp_x0_alone"] = p.vjp(*args(d), gw, w=w, want=("x0",), **kw)["x0"]
+        if hasattr(p.lib, "cmpc_refine_run"):
+            for mode, sel in (("w", dict(w=w)), ("free", dict(w=w, faces=torch.zeros_like(held))),
+                              ("check", dict(w=w, max_rounds=0))):
+                wo = w.clone()
+                st = torch.zeros(len(w), dtype=torch.int32, device=w.device)
+                g = p.refine(*args(d), **dict(dict(max_rounds=8), **sel), w_out=wo, status=st,
+                             want=_lib.REFINE_OUTPUTS, **kw)
+                out.update({f"refine_{mode}_{k}": v for k, v in g.items()})
+                out.update({f"refine_{mode}_w_out": wo, f"refine_{mode}_status": st})
         torch.cuda.synchronize()
         res.update({f"{tag}_{k}": v.cpu().numpy() for k, v in out.items()})
 
