@@ -1,5 +1,5 @@
 // cmpc_diag.h -- the diagnostic builds of the solve kernels, kept out of the product text.
-// Included by cmpc_wave.hip inside namespace cmpc, after the wave helpers (opaque_lane,
+// Included by cmpc_wave_prims.h inside namespace cmpc, after the wave helpers (opaque_lane,
 // wave_sum, uniformf, WSYNC).  solve_instance, its phases and polish_check call the hooks of
 // one `Diag` object and the trace macros; in a product build every hook is an empty inline
 // function, the object has no data and the macros expand to nothing.
@@ -13,7 +13,7 @@
 //   -DCMPC_DIAG_TIMES    status = start, iters = duration on the 100 MHz constant clock
 //   -DCMPC_POISON_LDS / -DCMPC_POISON_PARK   NaN into the float scratch / the wave's park slab
 //                        before every instance (W = 1)
-// (-DCMPC_STAMPS: the CMPC_T0 / CMPC_ACC / CMPC_CNT one-liners of cmpc_wave.hip.)
+// (-DCMPC_STAMPS: the CMPC_T0 / CMPC_ACC / CMPC_CNT one-liners of cmpc_wave_prims.h.)
 #pragma once
 
 #if defined(CMPC_TRACE_IDS) && !defined(CMPC_TRACE)

@@ -3,7 +3,7 @@
 // into it, the instance's constants with the validity decision, and the face rule.
 // Included by cmpc_kkt.hip and, through cmpc_lq.h (what the last three share beyond this), by the
 // other three only; the solve kernels have their own inputs and an fp32 face rule with a slack
-// (cmpc_device.h, cmpc_wave.hip).
+// (cmpc_device.h, cmpc_polish.h faces_at).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -10,9 +10,10 @@
 //   SYMV    out = M in (team_symv_part, team_symv_reduce),
 //   PSTORE / PLOAD  park / restore the inverse,
 // each wave on its own share of the lower-triangle tiles, held in its registers.  (The one-wave
-// kernels keep block LDL' factors instead, cmpc_wave.hip ldl_tiles / ldl_apply.)  The arithmetic
-// of the block-row backward pass and of a pivot block is cmpc_wave.hip's (state_operands,
-// blockrow_*, pivot_block); this file owns the slot loops, the barriers and the read scheduling.
+// kernels keep block LDL' factors instead, cmpc_factor.h ldl_tiles / ldl_apply.)  The arithmetic
+// of the block-row backward pass is cmpc_condense.h's (state_operands, blockrow_*), that of a
+// pivot block cmpc_factor.h's (pivot_block, panel_row); this file owns the slot loops, the
+// barriers and the read scheduling.
 //
 // Tile ownership: the tile COLUMNS J and TT-1-J form a pair of exactly TT+1 tiles; pair pr goes
 // to wave pr % W as its local pair pr / W.  Local slot l of a pair is tile
@@ -29,18 +30,12 @@
 // team block (panel, partial sums, scratch); the leader mutates the instance's LDS image only
 // between commands, while the helpers wait at the next command's barrier.
 //
-// This file is compiled as part of cmpc_wave.hip (single translation unit).
+// Included by cmpc_solve.h, whose phases call the leader's side (team_*_lead, team_issue).
+#pragma once
+#include "cmpc_condense.h"
+#include "cmpc_factor.h"
 
-template <int NC, int W>
-struct TeamCfg {
-  static constexpr int TT = NC / 16;
-  static constexpr int NPAIR = TT / 2;
-  static constexpr int PPW = (NPAIR + W - 1) / W;  // column pairs per wave
-  // register tiles per wave (W = 1: the one-wave kernels, every lower tile)
-  static constexpr int SLOTS = W == 1 ? TT * (TT + 1) / 2 : PPW * (TT + 1);
-  static constexpr int SLAB = W * SLOTS * 256;     // park slab of the team (floats)
-  static_assert(W == 1 || TT % 2 == 0, "team mode pairs tile columns");
-};
+namespace cmpc {
 
 enum : int { kOpExit = 0, kOpFactor = 1, kOpSymv = 2, kOpParkStore = 3, kOpParkLoad = 4 };
 
@@ -228,7 +223,7 @@ __device__ __forceinline__ void team_scale(TeamSmem<NC, W>& ts, f4 (&M)[TeamCfg<
 
 // ------------------------------------------------------------------------------------------
 // FACTOR: M <- -(H + diag(Rt) + shift)^-1 share of this wave: the closed-form or block-row
-// condensation (cmpc_wave.hip condense_tiles_nil / condense_tiles_bc, per slot; the closed form is
+// condensation (cmpc_condense.h condense_tiles_nil / condense_tiles_bc, per slot; the closed form is
 // restated here, a shared form measured slower), then the 4-pivot block sweep of every owned tile
 // ------------------------------------------------------------------------------------------
 template <int NC, int W, int WV>
@@ -248,12 +243,12 @@ __device__ __forceinline__ void team_factor(Smem<NC>& s, TeamSmem<NC, W>& ts, co
   for (int t = 0; t < T::SLOTS; ++t) M[t] = f4{0.f, 0.f, 0.f, 0.f};
   float aA[3], aT[3];
   f4 q2;
-  state_operands(s, g, c, aA, aT, q2);  // (cmpc_wave.hip: the K = 12 state layout)
+  state_operands(s, g, c, aA, aT, q2);  // (cmpc_condense.h: the K = 12 state layout)
   float* Cs = s.G;  // C_i columns (or V = N b: the closed form), param-major [p][12]
   CMPC_T0(t_f0);
   const int sc = lane_state(c);
   if (uniform(s.nil)) {
-    // ---- closed form for a nilpotent step (cmpc_wave.hip condense_tiles_nil): V = N b by the
+    // ---- closed form for a nilpotent step (cmpc_condense.h condense_tiles_nil): V = N b by the
     // chunk's wave (J % W), one barrier, then every owned tile is six MFMAs
     {
       float aN[3];
@@ -756,3 +751,5 @@ __device__ __forceinline__ void team_helpers(Smem<192>& s3, TeamSmem<192, W>& t3
     }
   }
 }
+
+}  // namespace cmpc

@@ -1,7 +1,8 @@
 """NumPy model of the HIP solver's algorithm (TEST INFRASTRUCTURE).
 
-Mirrors ``convex-mpc-unitree-go2_amd/csrc/cmpc_wave.hip`` step for step (condensed
-free-force ADMM with an fp32 preconditioner, accurate error-coordinate gradient, active-set
+Mirrors the solve kernels (``convex-mpc-unitree-go2_amd/csrc/cmpc_solve.h`` solve_instance and
+the phase headers it includes: cmpc_condense.h, cmpc_gradient.h, cmpc_polish.h) step for step
+(condensed free-force ADMM with an fp32 preconditioner, accurate error-coordinate gradient, active-set
 polish with iterative refinement) so the algorithm's logic can be exercised on CPU.  Not the
 oracle: the oracle is ``oracle/tight_solver.py``.
 """
@@ -170,7 +171,7 @@ def solve(inst, p: Params):
     tri = [(k, l) for k in range(N) for l in range(4) if stance[k, l]]
 
     def make_basis(code):
-        """Reduced basis of the faces in `code` (cmpc_wave.hip polish_setup) and its factorization:
+        """Reduced basis of the faces in `code` (cmpc_polish.h polish_setup) and its factorization:
         u = T v + t0; pidx[t] = (px, py, pz) of triple t (-1: no param)."""
         stats['fact'] += 1
         if p.trace is not None:
@@ -247,7 +248,7 @@ def solve(inst, p: Params):
 
     def refine(bs, v):
         step = np.inf; prev = np.inf
-        for q in range(p.polish_refine + 4):   # cmpc_wave.hip kRefineExtra, kRefineRate
+        for q in range(p.polish_refine + 4):   # cmpc_instance.h kRefineExtra, kRefineRate
             stats['refine'] += 1
             u = expand(bs, v)
             g, _ = gradient(A, B, d, p.Q, p.R, u.reshape(N, 12))
@@ -261,7 +262,7 @@ def solve(inst, p: Params):
         return v, step
 
     def check(bs, v, code, step, u_in=None):
-        """KKT check of the faces in `code` at v (forces from the basis, cmpc_wave.hip
+        """KKT check of the faces in `code` at v (forces from the basis, cmpc_polish.h
         polish_check); returns ok, u, the repaired code, loose."""
         u = expand(bs, v) if u_in is None else u_in.astype(F32)
         g, _ = gradient(A, B, d, p.Q, p.R, u.reshape(N, 12))
@@ -290,7 +291,7 @@ def solve(inst, p: Params):
             if not sy and abs(fy) > p.mu * fz + tol_p: ok = False; nc |= (8 if fy > 0 else 16)
             if not (c & 1) and fz < p.fz_min - tol_p: ok = False; nc |= 1
             newcode[ti] = nc
-            # largest relative violation (cmpc_wave.hip polish_check `viol`)
+            # largest relative violation (cmpc_polish.h polish_check `viol`)
             vv = max(-lx / gs if sx else 0.0, -ly / gs if sy else 0.0,
                      -l0 / gs if c & 1 else 0.0,
                      0.0 if sx else (abs(fx) - p.mu * fz) / us,
@@ -307,7 +308,7 @@ def solve(inst, p: Params):
 
     def face_constraints(bs, code_old, code_new):
         """Face additions (code_old -> code_new, no drops) as equalities a'v = c on the basis
-        params (cmpc_wave.hip face downdates)."""
+        params (cmpc_polish.h face downdates)."""
         cons = []
         for ti, (k, l) in enumerate(tri):
             add = int(code_new[ti]) & ~int(code_old[ti])
@@ -551,7 +552,7 @@ def solve(inst, p: Params):
 
     failed_starts = []
     # the NC >= 128 bins (nf > 96) start from rho / 2 and return to rho after their first
-    # failed polish session (cmpc_wave.hip session_failed, Ctl::rho_low)
+    # failed polish session (cmpc_solve.h session_failed, Ctl::rho_low)
     # the NC <= 128 bins polish one stable iteration earlier (cmpc_wave.hip CMPC_LIGHT_STABLE_DELTA)
     pstable = max(1, p.stable_checks - (p.light_stable_delta if nf <= 128 else 0))
     rho_low = nf > 96
@@ -580,12 +581,12 @@ def solve(inst, p: Params):
         else:
             stable = 0
         prev_code = code
-        backoff = pstable << min(len(failed_starts), p.backoff_cap)   # cmpc_wave.hip kBackoffCap
+        backoff = pstable << min(len(failed_starts), p.backoff_cap)   # cmpc_instance.h kBackoffCap
         if stable >= pstable * p.stable_grow ** min(len(failed_starts), p.backoff_cap) and it - last_pol >= backoff:
             last_pol = it
             # a session: polish ADMM's face set, then repair it.  A set that started a failed
             # session before is polished once more without repairs; a repair that returns to a
-            # set this session already tried ends the session (cmpc_wave.hip kFailMem/kTryMem).
+            # set this session already tried ends the session (cmpc_instance.h kFailMem/kTryMem).
             if p.weak_base > 0:
                 _, weak_code[0] = project((xr + F32(1 - p.weak_base) * y / F32(rho)).reshape(-1, 3),
                                           p.mu, p.fz_min)
@@ -593,7 +594,8 @@ def solve(inst, p: Params):
             seen = start in failed_starts[-4:]
             tried = [start]
             stats['sessions'] += 1
-            # the ADMM inverse is parked only where a failure restores it (cmpc_wave.hip)
+            # the ADMM inverse is parked only where a failure restores it (cmpc_solve.h
+            # start_session)
             parked = not rho_low and len(failed_starts) > 0
             budget = 0 if seen else (min(p.repairs, p.late_repairs) if len(failed_starts) >= 2 else p.repairs)
             ok, u, _, loose = session(z, code, budget, tried)
@@ -605,7 +607,7 @@ def solve(inst, p: Params):
             if not seen:
                 failed_starts.append(start)
             if len(failed_starts) == 1 and not seen:
-                # the first failed session: continue at 4 x rho0 (cmpc_wave.hip kFailRho)
+                # the first failed session: continue at 4 x rho0 (cmpc_instance.h kFailRho)
                 rho_low = False; rho = p.fail_rho * p.rho; L = admm_matrix(rho)
             elif rho_low:
                 rho_low = False; rho = p.rho; L = admm_matrix(rho)

@@ -123,6 +123,32 @@ def test_shorter_horizon_plan():
         assert rel_err_U(w[i:i + 1], _tight(b, i)[None], N=8)[0] <= TOL_U
 
 
+def test_short_horizons():
+    """Horizons N = 1 and 5 (below 16 and no power of two), where the gradient scans'
+    `(1 << l) >= N` cut and the `c < N` masks decide (cmpc_gradient.h gradient): the nilpotent
+    step matrix as generated and the attitude-damped one of test_general_step_matrix, each with
+    team mode forced and off.  Every instance is verified and within 1e-4 of its certified
+    optimum."""
+    from cmpc import Plan, SolverParams, solve_batch, synth
+    keys = ("Ad", "Bd", "gd", "x0", "xref", "contact")
+    for N in (1, 5):
+        b = synth.make_batch(8, seed=11, mixed=True, N=N)
+        for damped in (False, True):
+            if damped:
+                for r in range(3, 6):
+                    b["Ad"][:, r, r] = 0.999
+            ref = np.stack([_tight(b, i) for i in range(8)])
+            for team in (1 << 40, 0):
+                p = Plan(SolverParams(N=N, max_batch=16))
+                p.set_team(team)
+                w, st, it = solve_batch({k: b[k] for k in keys}, plan=p)
+                err = rel_err_U(w, ref, N=N)
+                print("N", N, "damped", damped, "team", team != 0, "status", st.tolist(),
+                      "iters", it.tolist(), "max rel err", float(err.max()))
+                assert np.all(st == 1), (N, damped, team, st.tolist())
+                assert err.max() <= TOL_U, (N, damped, team, float(err.max()))
+
+
 def test_deterministic(plan):
     from cmpc import solve_batch, synth
     b = synth.make_config(2, B=512)
@@ -237,7 +263,7 @@ def test_check_termination_reference_interval():
 def test_general_step_matrix(plan, reps):
     """A step matrix that is NOT I + N with N^2 = 0 takes the general condensation and the
     gradient's squared powers of A (the reference's nilpotent ZOH takes the closed forms,
-    cmpc_wave.hip condense_tiles_nil): a perturbed Ad (an attitude-damping term on the Euler
+    cmpc_condense.h condense_tiles_nil): a perturbed Ad (an attitude-damping term on the Euler
     rates, A[3:6, 3:6] = 0.999 I) is solved to 1e-4 of ITS certified optimum, in latency mode and
     replicated past the latency threshold (throughput mode)."""
     from cmpc import solve_batch, synth
@@ -259,7 +285,7 @@ def test_general_step_matrix(plan, reps):
 def test_general_step_matrix_one_wave_latency():
     """The same eight damped instances (free-force counts 96 .. 150: bins NC 96, 128, 144, 160)
     with team mode off: a small batch then runs one wave per QP in latency mode, where the NC 96 /
-    128 kernel condenses a general A by the block-row form (cmpc_wave.hip condense_tiles_bc), which
+    128 kernel condenses a general A by the block-row form (cmpc_condense.h condense_tiles_bc), which
     the default team rule never reaches.  Both group kernels must be the ones launched.  The
     small-batch rule of parity_util.assert_verified (at most one status 2) and test_gpu_terrain's
     bars: status 1 within 1e-4 of the certified optimum, status 2 within 1e-3."""

@@ -128,7 +128,7 @@ def test_warm_next_tick(plan):
     assert itw.mean() < itc.mean(), (itw.mean(), itc.mean())
     assert np.mean(itw == 0) > 0.95, np.unique(itw, return_counts=True)
     # the warm tail is no worse than cold: a warm start whose face set fails its polish session
-    # restarts as the cold solve (cmpc_wave.hip warm_restart, Polish::kWarmRestart)
+    # restarts as the cold solve (cmpc_solve.h warm_restart, Polish::kWarmRestart)
     assert itw.max() <= itc.max(), (int(itw.max()), int(itc.max()), int(itw.argmax()))
     # every instance, not only the certified subset: where cold and warm both verified their
     # answer (status 1, each within 1e-4 of the same unique optimum), they agree within 2e-4

@@ -43,7 +43,7 @@ def test_algorithm_model_reaches_parity():
 
 
 def test_algorithm_model_face_downdates():
-    """tests/algo_spec.py with the kernel's face downdates (cmpc_wave.hip face_downdate) and its
+    """tests/algo_spec.py with the kernel's face downdates (cmpc_polish.h face_downdate) and its
     fp32 sweep inverse: the same certified optima, and the pure face-adding repairs skip their
     factorization (hard fixture instances, which repair)."""
     import algo_spec
