@@ -18,6 +18,12 @@ namespace cmpc {
 // + diag(Rt) + shift, identity on padding.  Only the diagonal tiles and the tile rows that reach
 // the padding (a lower tile's padded columns imply padded rows) have anything to change: the
 // interior off-diagonal tiles are skipped by a uniform test instead of testing every element.
+// The elements that remain are settled by selects, not branches.  A lane holds a diagonal element
+// only where c >> 2 == g, and then it is that of row 16 I + c: one read of Rt per tile row (its
+// value is unused in the other lanes; four rows per lane as one 16-byte read cost the NC 128
+// kernel five more spilled registers).  A diagonal element takes v + (Rt + shift), padding takes
+// the identity, and every other element keeps its value (selected, not v + 0: a -0 stays -0).
+// Per element branches cost a trot instance 32 serial LDS round trips and ~300 exec branches here.
 template <int NC>
 __device__ __forceinline__ void condense_finish(Smem<NC>& s, f4 (&M)[Cfg<NC>::NTL], int n,
                                                 float shift) {
@@ -26,6 +32,7 @@ __device__ __forceinline__ void condense_finish(Smem<NC>& s, f4 (&M)[Cfg<NC>::NT
   const int g = lane >> 4, c = lane & 15;
 #pragma unroll
   for (int I = 0; I < C::TT; ++I) {
+    const float rs = s.Rt[16 * I + c] + shift;
 #pragma unroll
     for (int J = 0; J <= I; ++J) {
       if (J != I && 16 * I + 16 <= n) continue;  // uniform: interior off-diagonal tile
@@ -34,8 +41,14 @@ __device__ __forceinline__ void condense_finish(Smem<NC>& s, f4 (&M)[Cfg<NC>::NT
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int row = 16 * I + 4 * g + q;
-        if (row >= n || col >= n) v[q] = (row == col) ? 1.f : 0.f;
-        else if (row == col) v[q] += s.Rt[row] + shift;
+        const bool pad = row >= n || col >= n;
+        if (J == I) {  // compile-time after unrolling
+          const bool dg = 4 * g + q == c;
+          const float dv = v[q] + rs;
+          v[q] = pad ? (dg ? 1.f : 0.f) : (dg ? dv : v[q]);
+        } else {
+          v[q] = pad ? 0.f : v[q];
+        }
       }
       M[tile_index(I, J)] = v;
     }
@@ -164,30 +177,49 @@ __device__ __forceinline__ void condense_tiles_fwd(Smem<NC>& s, const KParams& P
 
 // Diagonal tiles of the block-row and closed-form condensations, which fill only the entries
 // whose column step <= row step: entry (r, c) with step(c) > step(r) is the mirror of (c, r).
-// Each tile turns through a 16 x 16 scratch in the G slab (C and V are dead by then).
+// The tiles turn through 16 x 16 scratches in the G slab (C and V are dead by then: the tile
+// loops have read them), as many at a time as the slab holds -- one write / read round trip per
+// batch instead of one per tile.  A lane's four transposed entries and its four row steps are
+// one 16-byte read each.
 template <int NC>
 __device__ __forceinline__ void mirror_diagonals(Smem<NC>& s, f4 (&M)[Cfg<NC>::NTL], int n, int N) {
   using C = Cfg<NC>;
+  // tiles per batch: the fewest batches the slab allows, of equal size (NC 128: two of four)
+  constexpr int kFit = 12 * NC / 256, kBatches = (C::TT + kFit - 1) / kFit;
+  constexpr int BT = (C::TT + kBatches - 1) / kBatches;
+  static_assert(BT >= 1 && BT * 256 <= 12 * NC, "the batch fits the G slab");
+  typedef int i4 __attribute__((ext_vector_type(4)));
   const int lane = opaque_lane();
   const int g = lane >> 4, c = lane & 15;
   WSYNC();
   float* T = s.G;
 #pragma unroll
-  for (int I = 0; I < C::TT; ++I) {
-    if (16 * I >= n) continue;  // uniform
-    f4 v = M[tile_index(I, I)];
+  for (int I0 = 0; I0 < C::TT; I0 += BT) {
+    if (16 * I0 >= n) continue;  // uniform
 #pragma unroll
-    for (int q = 0; q < 4; ++q) T[(4 * g + q) * 16 + c] = v[q];
-    WSYNC();
-    const int pc = 16 * I + c;
-    const int kc = (pc < n) ? s.par[pc] : N;
+    for (int I = I0; I < I0 + BT && I < C::TT; ++I) {
+      if (16 * I >= n) continue;  // uniform
+      const f4 v = M[tile_index(I, I)];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int pr = 16 * I + 4 * g + q;
-      const int kr = (pr < n) ? s.par[pr] : N;
-      if (kc > kr) v[q] = T[c * 16 + 4 * g + q];
+      for (int q = 0; q < 4; ++q) T[256 * (I - I0) + (4 * g + q) * 16 + c] = v[q];
     }
-    M[tile_index(I, I)] = v;
+    WSYNC();
+#pragma unroll
+    for (int I = I0; I < I0 + BT && I < C::TT; ++I) {
+      if (16 * I >= n) continue;  // uniform
+      f4 v = M[tile_index(I, I)];
+      const int pc = 16 * I + c;
+      const int kc = (pc < n) ? s.par[pc] : N;
+      const i4 kr4 = *reinterpret_cast<const i4*>(&s.par[16 * I + 4 * g]);
+      const f4 tr = *reinterpret_cast<const f4*>(&T[256 * (I - I0) + c * 16 + 4 * g]);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int pr = 16 * I + 4 * g + q;
+        const int kr = (pr < n) ? kr4[q] : N;
+        v[q] = (kc > kr) ? tr[q] : v[q];
+      }
+      M[tile_index(I, I)] = v;
+    }
     WSYNC();
   }
 }
@@ -312,8 +344,6 @@ __device__ __forceinline__ void condense_tiles_nil(Smem<NC>& s, const KParams& P
   const int N = P.N;
   n = uniform(n);
   const int TA = (n + 15) >> 4;
-#pragma unroll
-  for (int t = 0; t < C::NTL; ++t) M[t] = f4{0.f, 0.f, 0.f, 0.f};
   float* Vs = s.G;  // V = N b, param-major [p][12] (the G slab is free while condensing)
   {
     // K = 12 state layout (as condense_tiles_fwd): accumulator position 4g + q holds state 3g + q
@@ -360,19 +390,24 @@ __device__ __forceinline__ void condense_tiles_nil(Smem<NC>& s, const KParams& P
   }
 #pragma unroll
   for (int I = 0; I < C::TT; ++I) {
-    if (I >= TA) continue;  // uniform
+    if (I >= TA) {  // uniform: a padding tile row receives no product
+#pragma unroll
+      for (int J = 0; J <= I; ++J) M[tile_index(I, J)] = f4{0.f, 0.f, 0.f, 0.f};
+      continue;
+    }
     float x[3], y[3];
     {
       const int p = 16 * I + c;
       const bool ok = p < n;
       const int k = ok ? s.par[p] : 0;
-      const float kf = (float)k;
       float S0, S1, S2;  // sum_{t=k}^{N-1} 1, t, t^2
       step_sums(k, N, S0, S1, S2);
 #pragma unroll
       for (int q = 0; q < 3; ++q) {
-        const float v = ok ? Vs[p * 12 + 3 * g + q] : 0.f;
-        const float u = ok ? fmaf(-kf, v, s.Bt[p * kBS + 3 * g + q]) : 0.f;
+        // the row's (u, v) are its chunk's column operands: the same expression on the same
+        // values, so they are taken from uc / vc instead of seven more LDS reads per tile row
+        const float v = vc[I][q];
+        const float u = uc[I][q];
         x[q] = q2[q] * fmaf(S0, u, S1 * v);
         y[q] = q2[q] * fmaf(S1, u, S2 * v);
       }
@@ -385,7 +420,9 @@ __device__ __forceinline__ void condense_tiles_nil(Smem<NC>& s, const KParams& P
         u[q] = uc[J][q];
         v[q] = vc[J][q];
       }
-      f4 acc = M[tile_index(I, J)];
+      // the tile's first product starts from a zero accumulator operand (0 + x u rounds as the
+      // accumulate into a zeroed tile did): no tile is zeroed before the loop
+      f4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int q = 0; q < 3; ++q) acc = mfma4(x[q], u[q], acc);
 #pragma unroll

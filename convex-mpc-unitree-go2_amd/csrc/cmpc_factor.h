@@ -4,6 +4,13 @@
 
 namespace cmpc {
 
+// Element c & 3 of a diagonal tile's register: the matrix diagonal in the lanes with c >> 2 == g
+// (lane (g, c) holds rows 4g .. 4g + 3 of column c), by selects
+__device__ __forceinline__ float diag_element(const f4& d, int c) {
+  const int qs = c & 3;
+  return qs == 0 ? d[0] : qs == 1 ? d[1] : qs == 2 ? d[2] : d[3];
+}
+
 // ---- software-pipelined sweep (bins up to kSweepPipeMaxNC; measured +3-5 % on NC = 128, and
 // -5 % on cfg2 when also used for the 1-wave-per-SIMD bins, whose registers it spills) ----
 constexpr int kSweepPipeMaxNC = 128;
@@ -195,15 +202,14 @@ __device__ __forceinline__ void ldl_tiles(SM& s, f4 (&M)[Cfg<NC>::NTL], int n) {
   const int g = lane >> 4, c = lane & 15;
   n = uniform(n);
   const int TA = (n + 15) >> 4;
-  // unit-diagonal scaling (padding: 1)
+  // unit-diagonal scaling (padding: 1): the lanes with c >> 2 == g hold the diagonal, as
+  // element c & 3 -- one select, one rsqrt and one masked store per tile row
 #pragma unroll
   for (int I = 0; I < C::TT; ++I) {
-    const f4 d = M[tile_index(I, I)];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int p = 16 * I + c;
-      if (4 * g + q == c) s.ds[p] = (p < n && d[q] > 0.f) ? rsqrtf(d[q]) : 1.f;
-    }
+    const float dg = diag_element(M[tile_index(I, I)], c);
+    const int p = 16 * I + c;
+    const float r = (p < n && dg > 0.f) ? rsqrtf(dg) : 1.f;
+    if ((c >> 2) == g) s.ds[p] = r;
   }
   WSYNC();
 #pragma unroll
@@ -229,16 +235,30 @@ __device__ __forceinline__ void ldl_tiles(SM& s, f4 (&M)[Cfg<NC>::NTL], int n) {
     sweep_block_plain<NC, 0>(s, M, ng, TA, g, c);
   }
   // undo the scaling: the diagonal tiles hold -(scaled D_K^-1), the tiles below them the
-  // scaled L~ = S^-1 L S
+  // scaled L~ = S^-1 L S.  There are only NC distinct reciprocals 1 / ds[p]: each is divided out
+  // once, by lane p % 64, and a lane reads its four as one 16-byte read per tile row (every lane
+  // dividing its own four per tile row was 4 TT full-precision divisions per lane).  They go
+  // through the panel, which is the sweep's own scratch: its last read is the last pivot step's,
+  // above, and nothing outside the sweep reads it before writing it.
+  float* rinvs = s.pan;
+  WSYNC();
+  // (the lane's coordinates re-derived: the sweep's do not stay live into this pass, which left
+  // the NC 192 kernel without a spilled register)
+  const int lane_r = opaque_lane();
+  const int g_r = lane_r >> 4, c_r = lane_r & 15;
+#pragma unroll
+  for (int p0 = 0; p0 < NC; p0 += 64) {
+    const int p = p0 + lane_r;
+    if (p < NC) rinvs[p] = 1.f / s.ds[p];
+  }
+  WSYNC();
 #pragma unroll
   for (int I = 0; I < C::TT; ++I) {
-    const f4 ri = *reinterpret_cast<const f4*>(&s.ds[16 * I + 4 * g]);
-    f4 rinv;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) rinv[q] = 1.f / ri[q];
+    const f4 ri = *reinterpret_cast<const f4*>(&s.ds[16 * I + 4 * g_r]);
+    const f4 rinv = *reinterpret_cast<const f4*>(&rinvs[16 * I + 4 * g_r]);
 #pragma unroll
     for (int J = 0; J <= I; ++J) {
-      const float cj = s.ds[16 * J + c];
+      const float cj = s.ds[16 * J + c_r];
       f4& m = M[tile_index(I, J)];
 #pragma unroll
       for (int q = 0; q < 4; ++q) m[q] *= (J < I) ? rinv[q] * cj : -(ri[q] * cj);

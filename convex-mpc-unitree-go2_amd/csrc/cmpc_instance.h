@@ -125,7 +125,7 @@ struct Smem {
   float Q2[12];                    // KParams copies (indexed at run time -> keep out of kernarg),
                                    // or the instance's own 2Q / 2R (Inputs::Q / R, stage_instance)
   float R2[12];
-  int par[NC];                     // param -> step k
+  alignas(16) int par[NC];         // param -> step k
   int off[kMaxN + 1];              // first param of step k
   int nil;                         // A = I + N with N^2 = 0 (nilpotent_step): closed forms apply
   int tri[kMaxTri];                // stance triple t -> 4k + leg

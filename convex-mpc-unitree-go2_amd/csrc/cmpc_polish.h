@@ -444,7 +444,11 @@ __device__ __forceinline__ bool face_downdate(Smem<NC>& s, const Terrain& T, con
     if (nadd + F > dd_max(NC)) return false;  // (uniform)
     if (owns && add) {
       // a face with no second param has p2 = p1 and coefficient 0
-      const float mu = T.mu, fzmin = T.fz_min;
+      // (fz_min's vector copy is made here: hoisted to the instance loop's head it stayed live
+      // for the whole solve and was one more spilled register of the NC 128 kernel)
+      const float mu = T.mu;
+      float fzmin = T.fz_min;
+      asm volatile("" : "+v"(fzmin));
       const int pk = s.fpk[lane];
       const int px = pk & 255, py = (pk >> 8) & 255, pz = (pk >> 16) & 255;
       if (add & 1) {  // (first: a friction face added with it then reads fz = fz_min)

@@ -487,7 +487,11 @@ __device__ __forceinline__ void team_factor(Smem<NC>& s, TeamSmem<NC, W>& ts, co
         if (16 * I < n && kcv > krv) m[q] = tr[h][q];
         if (row >= n || pc >= n) m[q] = (row == pc) ? 1.f : 0.f;
         else if (row == pc) m[q] += rt[h] + shift;
-        if (4 * g + q == c) ts.ds[pc] = (pc < n && m[q] > 0.f) ? rsqrtf(m[q]) : 1.f;
+      }
+      {  // the sweep's scaling from the finished diagonal (as ldl_tiles)
+        const float dg = diag_element(m, c);
+        const float r = (pc < n && dg > 0.f) ? rsqrtf(dg) : 1.f;
+        if ((c >> 2) == g) ts.ds[pc] = r;
       }
       M[base + ld[h]] = m;
     }
