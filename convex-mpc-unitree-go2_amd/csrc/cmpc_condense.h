@@ -376,12 +376,16 @@ __device__ __forceinline__ void condense_tiles_nil(Smem<NC>& s, const KParams& P
   // the column operands (u, v) of every chunk, once: each is reused by every tile row below it
   // (loaded per tile instead: 7 LDS reads between every tile's MFMAs; caching them took config 3
   // 9.09 -> 8.60 ms, config 2 at 65,536 10.55 -> 9.99 ms, A/B in one gpurun call)
+  // (and the chunk's step k: the tile row I = J below takes its sums over the steps from it,
+  // not from another LDS read per tile row)
   float uc[C::TT][3], vc[C::TT][3];
+  int kc[C::TT];
 #pragma unroll
   for (int J = 0; J < C::TT; ++J) {
     const int p = 16 * J + c;
     const bool ok = J < TA && p < n;
-    const float kf = ok ? (float)s.par[p] : 0.f;
+    kc[J] = ok ? s.par[p] : 0;
+    const float kf = (float)kc[J];
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
       vc[J][q] = ok ? Vs[p * 12 + 3 * g + q] : 0.f;
@@ -397,11 +401,8 @@ __device__ __forceinline__ void condense_tiles_nil(Smem<NC>& s, const KParams& P
     }
     float x[3], y[3];
     {
-      const int p = 16 * I + c;
-      const bool ok = p < n;
-      const int k = ok ? s.par[p] : 0;
       float S0, S1, S2;  // sum_{t=k}^{N-1} 1, t, t^2
-      step_sums(k, N, S0, S1, S2);
+      step_sums(kc[I], N, S0, S1, S2);
 #pragma unroll
       for (int q = 0; q < 3; ++q) {
         // the row's (u, v) are its chunk's column operands: the same expression on the same

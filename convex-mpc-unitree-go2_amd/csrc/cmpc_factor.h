@@ -286,29 +286,53 @@ __device__ __forceinline__ void ldl_apply(SM& s, const f4 (&M)[Cfg<NC>::NTL], in
   float bc[C::TT];
 #pragma unroll
   for (int I = 0; I < C::TT; ++I) bc[I] = 0.f;
+  // `out` is zeroed once (it is never `in`): the block rows past the last real one stay so, and
+  // both loops leave them alone
+  if (4 * lane < NC) *reinterpret_cast<f4*>(&out[4 * lane]) = f4{0.f, 0.f, 0.f, 0.f};
+  // Only the last real block row has padding rows.  Its row masks, once per call: row 4 g + q of
+  // block TA - 1 for the forward pass, row c for the backward one; every block row above it is
+  // kept whole by the uniform test.
+  const int nl = n - 16 * (TA - 1);
+  const bool kr0 = 4 * g < nl, kr1 = 4 * g + 1 < nl, kr2 = 4 * g + 2 < nl, kr3 = 4 * g + 3 < nl;
+  const bool kc = c < nl;
+  // Forward, one block row ahead: the products of block row I + 1 with z_0 .. z_{I-1} are formed
+  // in block row I's basic block (each accumulator still in J order), beside the chain z_{I-1}
+  // -> z_I, which then holds only the last tile's FMAs, the row sums and the turn.  (Every block
+  // row's accumulators started as soon as each z_J is known would be 4 (TT - 1) live registers.)
+  f2 a01 = {0.f, 0.f}, a23 = {0.f, 0.f};  // block row I's products with z_0 .. z_{I-2}
 #pragma unroll
   for (int I = 0; I < C::TT; ++I) {
-    if (I >= TA) {  // padding rows: zero (uniform branch)
-      if (c == 0) *reinterpret_cast<f4*>(&out[16 * I + 4 * g]) = f4{0.f, 0.f, 0.f, 0.f};
-      continue;
-    }
+    if (I >= TA) continue;  // uniform
     f4 zr = *reinterpret_cast<const f4*>(&in[16 * I + 4 * g]);
+    f2 n01 = {0.f, 0.f}, n23 = {0.f, 0.f};
     if (I > 0) {
-      f2 r01 = {0.f, 0.f}, r23 = {0.f, 0.f};
+      const f4 ml = M[tile_index(I, I - 1)];
+      const f2 zl = {zc[I - 1], zc[I - 1]};
+      const f2 r01 = __builtin_elementwise_fma(f2{ml[0], ml[1]}, zl, a01);
+      const f2 r23 = __builtin_elementwise_fma(f2{ml[2], ml[3]}, zl, a23);
+      if (I + 1 < C::TT) {
 #pragma unroll
-      for (int J = 0; J < I; ++J) {
-        const f4 m = M[tile_index(I, J)];
-        const f2 zj = {zc[J], zc[J]};
-        r01 = __builtin_elementwise_fma(f2{m[0], m[1]}, zj, r01);
-        r23 = __builtin_elementwise_fma(f2{m[2], m[3]}, zj, r23);
+        for (int J = 0; J < I; ++J) {
+          const f4 m = M[tile_index(I + 1, J)];
+          const f2 zj = {zc[J], zc[J]};
+          n01 = __builtin_elementwise_fma(f2{m[0], m[1]}, zj, n01);
+          n23 = __builtin_elementwise_fma(f2{m[2], m[3]}, zj, n23);
+        }
       }
-      zr[0] -= row16_sum(r01[0]);
-      zr[1] -= row16_sum(r01[1]);
-      zr[2] -= row16_sum(r23[0]);
-      zr[3] -= row16_sum(r23[1]);
+      float s0 = r01[0], s1 = r01[1], s2 = r23[0], s3 = r23[1];
+      row16_sum4(s0, s1, s2, s3);
+      zr[0] -= s0;
+      zr[1] -= s1;
+      zr[2] -= s2;
+      zr[3] -= s3;
     }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) zr[q] = (16 * I + 4 * g + q < n) ? zr[q] : 0.f;
+    a01 = n01;
+    a23 = n23;
+    const bool whole = I < TA - 1;  // uniform
+    zr[0] = (whole | kr0) ? zr[0] : 0.f;
+    zr[1] = (whole | kr1) ? zr[1] : 0.f;
+    zr[2] = (whole | kr2) ? zr[2] : 0.f;
+    zr[3] = (whole | kr3) ? zr[3] : 0.f;
     // the block turns from rows to columns through `out` (a register turn -- DPP / permlane
     // swaps -- measured 1.3 % slower with this arithmetic, round 5; for the one-wave class alone
     // no gain on its kernel or on the step, profiles/heavy_paths_ab.txt)
@@ -316,21 +340,24 @@ __device__ __forceinline__ void ldl_apply(SM& s, const f4 (&M)[Cfg<NC>::NTL], in
     WSYNC();
     zc[I] = out[16 * I + c];
   }
-  // backward: x_I = D_I^-1 z_I - sum_{J > I} L_JI' x_J
+  // backward: x_I = D_I^-1 z_I - sum_{J > I} L_JI' x_J.  One LDS round trip per block row: z of
+  // the block row above is read together with this one's x (x_I is stored over z_I only)
+  f4 zr = {0.f, 0.f, 0.f, 0.f};
+  if (TA > 0) zr = *reinterpret_cast<const f4*>(&out[16 * (TA - 1) + 4 * g]);  // uniform
 #pragma unroll
   for (int I = C::TT - 1; I >= 0; --I) {
     if (I >= TA) continue;  // uniform
-    const f4 zr = *reinterpret_cast<const f4*>(&out[16 * I + 4 * g]);
     const f4 d = M[tile_index(I, I)];
     const float t =
         fmaf(d[3], zr[3], fmaf(d[2], zr[2], fmaf(d[1], zr[1], fmaf(d[0], zr[0], -bc[I]))));
     float xc = col4_sum(t);
-    xc = (16 * I + c < n) ? xc : 0.f;
+    xc = ((I < TA - 1) | kc) ? xc : 0.f;
     WSYNC();
     if (g == 0) out[16 * I + c] = xc;
     if (I == 0) break;
     WSYNC();
     const f4 xr = *reinterpret_cast<const f4*>(&out[16 * I + 4 * g]);
+    zr = *reinterpret_cast<const f4*>(&out[16 * (I - 1) + 4 * g]);
 #pragma unroll
     for (int J = 0; J < I; ++J) {
       const f4 m = M[tile_index(I, J)];

@@ -79,10 +79,20 @@ __device__ __forceinline__ void gradient_powers(SM& s, f4 (&pw)[4], f4 (&tw)[4])
 // from 40 to 57 VGPRs and a standing batch gains nothing.
 template <int NC, int W>
 constexpr bool kGradLat = W > 1 || (Cfg<NC>::WPE == 1 && NC <= 160);
-template <int NC, bool LAT = false, bool PREC = false>
+// The closing loop g = B~' lambda + R~ v with its trips unrolled (NC / 64, rounded up).  Not in
+// the NC 192 kernel: its three trips' operands in flight cost 12 spilled VGPRs where it has none.
+template <int NC>
+constexpr bool kCloseUnrolled = NC <= 160;
+// EPI (the closing loop's epilogue): called by every lane of every trip with its param p, the
+// gradient entry g[p] just formed and whether p < n (else p = 0 and g[p] is meaningless); what it
+// reads of param p travels with the loop's own LDS reads, and it stores only where p < n.
+struct NoEpilogue {
+  __device__ __forceinline__ void operator()(int, float, bool) const {}
+};
+template <int NC, bool LAT = false, bool PREC = false, class EPI = NoEpilogue>
 __device__ __forceinline__ void gradient(Smem<NC>& s, const KParams& P, int n, const float* vin,
                                          float* gout, const f4* pwc = nullptr,
-                                         const f4* twc = nullptr) {
+                                         const f4* twc = nullptr, EPI epi = EPI()) {
   CMPC_T0(t_gr);
   const int lane = opaque_lane();
   const int g = lane >> 4, c = lane & 15;
@@ -177,13 +187,7 @@ __device__ __forceinline__ void gradient(Smem<NC>& s, const KParams& P, int n, c
       // the same scans in float64; N u on the f64 matrix cores, whose D layout (row = g + 4 reg)
       // puts state 3g + reg of step c in register reg of lane (g, c), as above
       double u64[3];
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        double x = Eh[q], y;
-        row_scan2<false>(x, y);
-        Eh[q] = x;
-        u64[q] = y;
-      }
+      row_scan2x3<false>(Eh, u64);
       const int sr = ((c >> 2) < 3) ? 3 * (c & 3) + (c >> 2) : -1;  // state of A-operand row c
       d4 acc = {Eh[0], Eh[1], Eh[2], 0.0};
 #pragma unroll
@@ -195,14 +199,12 @@ __device__ __forceinline__ void gradient(Smem<NC>& s, const KParams& P, int n, c
 #pragma unroll
       for (int q = 0; q < 3; ++q) Et[q] = (float)acc[q];
     } else {
-    f4 u = {0.f, 0.f, 0.f, 0.f};
+    // S: inclusive prefix sum over the steps (lanes c of the DPP row), u: exclusive prefix sum
+    // of S; the three states' scans step together
+    float S[3] = {Et[0], Et[1], Et[2]}, u[3];
+    row_scan2x3<false>(S, u);
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      float x = Et[q], y;  // S: inclusive prefix sum over the steps (lanes c of the DPP row),
-      row_scan2<false>(x, y);  // u: exclusive prefix sum of S
-      Et[q] = x;
-      u[q] = y;
-    }
+    for (int q = 0; q < 3; ++q) Et[q] = S[q];
 #pragma unroll
     for (int q = 0; q < 3; ++q) Et = mfma4(aN[q], u[q], Et);
     }
@@ -210,14 +212,12 @@ __device__ __forceinline__ void gradient(Smem<NC>& s, const KParams& P, int n, c
 #pragma unroll
       for (int q = 0; q < 3; ++q) s.E[12 * c + 3 * g + q] = Et[q];
     }
-    f4 Lt = {0.f, 0.f, 0.f, 0.f}, v = {0.f, 0.f, 0.f, 0.f};
+    // R: inclusive suffix sum, v: exclusive suffix sum of R
+    float Rs[3], v[3];
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      float x = (c < N) ? s.Q2[3 * g + q] * Et[q] : 0.f, y;  // R: inclusive suffix sum,
-      row_scan2<true>(x, y);                                  // v: exclusive suffix sum of R
-      Lt[q] = x;
-      v[q] = y;
-    }
+    for (int q = 0; q < 3; ++q) Rs[q] = (c < N) ? s.Q2[3 * g + q] * Et[q] : 0.f;
+    row_scan2x3<true>(Rs, v);
+    f4 Lt = {Rs[0], Rs[1], Rs[2], 0.f};
 #pragma unroll
     for (int q = 0; q < 3; ++q) Lt = mfma4(aNt[q], v[q], Lt);
     if (c < N) {
@@ -268,8 +268,12 @@ __device__ __forceinline__ void gradient(Smem<NC>& s, const KParams& P, int n, c
   }
   }  // (general A)
   WSYNC();
-  for (int p = lane; p < n; p += 64) {  // g = B~' lambda + Rt v
-    const int k = s.par[p];
+  // g = B~' lambda + Rt v, 64 params per trip, predicated: a lane past n reads param 0 and
+  // step 0 and stores nothing
+  auto close_trip = [&](int p0) {
+    const bool ok = p0 + lane < n;
+    const int p = ok ? p0 + lane : 0;
+    const int k = ok ? s.par[p] : 0;
     const f4* l = reinterpret_cast<const f4*>(&s.L[12 * k]);
     f2 a2 = {s.Rt[p] * vin[p], 0.f};  // packed: even and odd states in the two halves
     const f4* bt = reinterpret_cast<const f4*>(&s.Bt[p * kBS]);
@@ -279,7 +283,15 @@ __device__ __forceinline__ void gradient(Smem<NC>& s, const KParams& P, int n, c
       a2 = __builtin_elementwise_fma(f2{bv[0], bv[1]}, f2{lv[0], lv[1]}, a2);
       a2 = __builtin_elementwise_fma(f2{bv[2], bv[3]}, f2{lv[2], lv[3]}, a2);
     }
-    gout[p] = a2[0] + a2[1];
+    const float gv = a2[0] + a2[1];
+    if (ok) gout[p] = gv;
+    epi(p, gv, ok);
+  };
+  if constexpr (kCloseUnrolled<NC>) {  // n <= NC: every trip's LDS reads issue together
+#pragma unroll
+    for (int p0 = 0; p0 < NC; p0 += 64) close_trip(p0);
+  } else {
+    for (int p0 = 0; p0 < n; p0 += 64) close_trip(p0);
   }
   WSYNC();
   CMPC_ACC(2, t_gr);

@@ -89,6 +89,7 @@ struct Ctl {
   bool polished = false;  // a polish pass accepted its point (the forces are in s.x)
   float rp = 0.f, rd = 0.f, np_ = 0.f, nd = 0.f;  // ADMM residuals and their scales
   float rho = 0.f;
+  float inv_rho = 0.f;    // 1 / rho, divided out where rho is set (set_rho)
   bool rho_low = false;   // still at the bin's reduced initial rho
   int stable = 0;         // ADMM iterations since the face set last changed
   bool refactor = false;  // (re)build + invert the matrix for the current basis
@@ -96,6 +97,8 @@ struct Ctl {
   int nact = 0;           // params of the current basis
   float shift = 0.f;      // sigma + rho (ADMM) or sigma (polish) on the matrix diagonal
   int it = 0;
+  int it_adapt = 0;       // it % P.adaptive_interval and it % P.check_every, counted along with
+  int it_check = 0;       // `it` (admm_iteration) instead of divided out every iteration
   int repairs_left = 0;
   int nadd = 0;           // faces added by downdates since the last factorization
   bool from_cand = false; // the polish refactored from a candidate that passed its check
@@ -112,6 +115,7 @@ struct Ctl {
 // follows, and the matrix is factorized anew
 __device__ __forceinline__ void set_rho(Ctl& c, const KParams& P, float rho, bool low) {
   c.rho = rho;
+  c.inv_rho = uniformf(1.f / rho);
   c.rho_low = low;
   c.shift = uniformf(P.sigma + c.rho);
   c.refactor = true;
@@ -657,22 +661,22 @@ __device__ __forceinline__ bool admm_iteration(Smem<NC>& s, const KParams& P, co
   const Terrain T = I.T;
   const float alpha = P.alpha;
   float rho = c.rho;
-  gradient<NC, kGradLat<NC, W>>(s, P, n, s.x, s.g, I.pwc, I.twc);
-  {
-    const int l = opaque_lane();
-    if (l < ntri) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const int p = 3 * l + a;
-        s.r[p] = rho * (s.z[p] - s.x[p]) - s.g[p] - s.y[p];
-      }
-    }
-  }
+  // the x-update's right-hand side r = rho (z - x) - g - y, entry by entry as the gradient's
+  // closing loop forms g (its z, x and y reads go out with the loop's own)
+  auto rhs = [&s, rho](int p, float gv, bool ok) {
+    const float rp = rho * (s.z[p] - s.x[p]) - gv - s.y[p];
+    if (ok) s.r[p] = rp;
+  };
+  gradient<NC, kGradLat<NC, W>, false, decltype(rhs)>(s, P, n, s.x, s.g, I.pwc, I.twc, rhs);
   apply_factors<NC, W>(s, ts, seq, M, n, s.r, s.dl);
   CMPC_T0(t_rest);
   const bool last = (it == P.max_iter);
-  const bool adapt = P.adaptive_interval > 0 && (it % P.adaptive_interval) == 0;
-  const float inv_rho = 1.f / rho;
+  // (every iteration passes here once, right after the driver's ++c.it: the two counters wrap
+  // where `it` reaches a multiple of their period)
+  if (++c.it_adapt == P.adaptive_interval) c.it_adapt = 0;
+  if (++c.it_check == P.check_every) c.it_check = 0;
+  const bool adapt = P.adaptive_interval > 0 && c.it_adapt == 0;
+  const float inv_rho = c.inv_rho;
   float lrp = 0.f, lrd = 0.f, lnp = 0.f, lnd = 0.f;
   bool changed = false;
   {
@@ -722,7 +726,7 @@ __device__ __forceinline__ bool admm_iteration(Smem<NC>& s, const KParams& P, co
   int need = pstable;  // (kStableGrow: the stable run required grows per failed session)
   for (int f = 0; f < min(c.nfail, kBackoffCap); ++f) need *= kStableGrow;
   if (c.stable >= need && !last && it - c.last_pol >= backoff &&
-      (P.check_every == 1 || it % P.check_every == 0)) {  // (OPTS check_termination)
+      (P.check_every == 1 || c.it_check == 0)) {  // (OPTS check_termination)
     do_pol = true;
     c.last_pol = it;
     c.stable = -backoff;

@@ -88,6 +88,15 @@ __device__ __forceinline__ float row16_sum(float v) {
   return v;
 }
 
+// row16_sum of four values at once, step by step across the four: each chain keeps its own
+// order, and no DPP step reads the register written by the instruction before it
+__device__ __forceinline__ void row16_sum4(float& a, float& b, float& c, float& d) {
+  a += dpp<0xB1>(a), b += dpp<0xB1>(b), c += dpp<0xB1>(c), d += dpp<0xB1>(d);
+  a += dpp<0x4E>(a), b += dpp<0x4E>(b), c += dpp<0x4E>(c), d += dpp<0x4E>(d);
+  a += dpp<0x141>(a), b += dpp<0x141>(b), c += dpp<0x141>(c), d += dpp<0x141>(d);
+  a += dpp<0x140>(a), b += dpp<0x140>(b), c += dpp<0x140>(c), d += dpp<0x140>(d);
+}
+
 // shift by D lanes along the DPP row, towards lower lanes (SHL: row_shl, lane c reads c + D) or
 // higher ones (row_shr, lane c reads c - D); a lane past the row reads zero
 template <bool SHL, int D>
@@ -117,6 +126,25 @@ __device__ __forceinline__ void row_scan2(T& x, T& y) {
   y += row_shift<SHL, 2>(y);
   y += row_shift<SHL, 4>(y);
   y += row_shift<SHL, 8>(y);
+}
+
+// row_scan2 of three values at once, step by step across the three: each chain keeps its own
+// order, and no DPP step reads the register written by the instruction before it
+template <bool SHL, class T>
+__device__ __forceinline__ void row_scan2x3(T (&x)[3], T (&y)[3]) {
+#define CMPC_SCAN_STEP(v, D)   \
+  _Pragma("unroll") for (int q = 0; q < 3; ++q) v[q] += row_shift<SHL, D>(v[q])
+  CMPC_SCAN_STEP(x, 1);
+  CMPC_SCAN_STEP(x, 2);
+  CMPC_SCAN_STEP(x, 4);
+  CMPC_SCAN_STEP(x, 8);
+#pragma unroll
+  for (int q = 0; q < 3; ++q) y[q] = row_shift<SHL, 1>(x[q]);
+  CMPC_SCAN_STEP(y, 1);
+  CMPC_SCAN_STEP(y, 2);
+  CMPC_SCAN_STEP(y, 4);
+  CMPC_SCAN_STEP(y, 8);
+#undef CMPC_SCAN_STEP
 }
 
 // sum over the 4 rows (lanes c, c+16, c+32, c+48), result in every lane
