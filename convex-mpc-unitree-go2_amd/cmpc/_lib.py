@@ -13,10 +13,6 @@ from pathlib import Path
 from .build import LIB
 
 ABI_VERSION = 6
-# ABI 5 (round 5) has this cmpc_params layout, bins and solve kernels (it lacks cmpc_plan_stats
-# and the certified status-1 bound): its builds load only for A/B experiments, with
-# CMPC_ALLOW_ABI5=1
-ABI_COMPAT = (5, 6) if os.environ.get("CMPC_ALLOW_ABI5") == "1" else (6,)
 NUM_STATS = 4  # CMPC_NUM_STATS
 CMPC_OK = 0
 
@@ -101,12 +97,6 @@ VJP_OUTPUTS = ("x0", "xref", "gd", "Q", "R", "mu", "fz_min", "Ad", "Bd")
 
 KKT_COLUMNS = ("cost", "stat", "prim", "comp")  # CMPC_KKT_COST .. CMPC_KKT_COMP
 
-EXPORTS = ("cmpc_params_default", "cmpc_plan_create", "cmpc_solve", "cmpc_plan_destroy",
-           "cmpc_build_dynamics", "cmpc_solve_warm", "cmpc_solve_ref", "cmpc_solve_io_run", "cmpc_kkt_run", "cmpc_gain_run", "cmpc_vjp_run", "cmpc_refine_run", "cmpc_generate_traj", "cmpc_leg_torque", "cmpc_srb_step",
-           "cmpc_plan_set_timing", "cmpc_plan_timing_read", "cmpc_plan_set_team", "cmpc_plan_team_batch",
-           "cmpc_plan_set_heavy_first",
-           "cmpc_plan_heavy_first_batch", "cmpc_plan_solve_kernel", "cmpc_plan_stats",
-           "cmpc_last_error", "cmpc_version")
 NUM_BINS = 5
 BIN_CAPS = (96, 128, 144, 160, 192)
 # solve kernels (timing slots): 0 = bins NC 128 + 96 (two waves per SIMD), 1 = bins NC 160 + 144,
@@ -115,6 +105,44 @@ NUM_SOLVE_KERNELS = 3
 KERNEL_BINS = ((1, 0), (3, 2), (4,))
 KERNEL_NAMES = ("solve_group_kernel<128, 96>", "solve_group_kernel<160, 144>",
                 "solve_group_kernel<192, 0>")
+
+
+def _prototypes() -> dict:
+    """Entry name -> (argtypes, restype) of every function include/cmpc.h declares."""
+    vp, i64, rc = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
+    ptr = ctypes.POINTER
+    table = {
+        "cmpc_params_default": ([ptr(CParams)], None),
+        "cmpc_plan_create": ([ptr(CParams), ptr(vp)], rc),
+        "cmpc_plan_destroy": ([vp], None),
+        "cmpc_solve": ([vp, i64] + [vp] * 10, rc),
+        "cmpc_solve_warm": ([vp, i64] + [vp] * 13, rc),
+        "cmpc_solve_ref": ([vp, i64] + [vp] * 13, rc),
+        "cmpc_build_dynamics": ([vp, i64, ctypes.c_float] + [vp] * 8, rc),
+        "cmpc_generate_traj": ([vp, i64, ctypes.c_double] + [vp] * 11, rc),
+        "cmpc_leg_torque": ([vp, i64, vp, vp, vp, i64] + [vp] * 12 + [ctypes.c_double, vp, vp], rc),
+        "cmpc_srb_step": ([vp, i64, rc, ctypes.c_double] + [vp] * 5 + [i64] + [vp] * 5, rc),
+        "cmpc_plan_set_timing": ([vp, rc], rc),
+        "cmpc_plan_timing_read": ([vp, ptr(ctypes.c_float), ptr(ctypes.c_int32)], rc),
+        "cmpc_plan_set_team": ([vp, i64], rc),
+        "cmpc_plan_team_batch": ([vp, ptr(i64)], rc),
+        "cmpc_plan_set_heavy_first": ([vp, i64], rc),
+        "cmpc_plan_heavy_first_batch": ([vp, ptr(i64)], rc),
+        "cmpc_plan_solve_kernel": ([vp, i64, rc], ctypes.c_char_p),
+        "cmpc_plan_stats": ([vp, ptr(ctypes.c_uint64), rc], rc),
+        "cmpc_last_error": ([], ctypes.c_char_p),
+        "cmpc_version": ([], ctypes.c_char_p),
+    }
+    # the struct entries: (plan, B, const io*, stream)
+    for name, io in (("cmpc_solve_io_run", CSolveIO), ("cmpc_kkt_run", CKktIO),
+                     ("cmpc_gain_run", CGainIO), ("cmpc_vjp_run", CVjpIO),
+                     ("cmpc_refine_run", CRefineIO)):
+        table[name] = ([vp, i64, ptr(io), vp], rc)
+    return table
+
+
+PROTOTYPES = _prototypes()
+EXPORTS = tuple(PROTOTYPES)
 
 _lib = None
 
@@ -132,74 +160,10 @@ def load(path: str | Path | None = None) -> ctypes.CDLL:
         raise RuntimeError(f"cmpc: HIP library {p} not built (run __graft_entry__.build() or "
                            f"python -m cmpc.build); there is no CPU fallback")
     lib = ctypes.CDLL(str(p))
-    vp = ctypes.c_void_p
-    lib.cmpc_params_default.argtypes = [ctypes.POINTER(CParams)]
-    lib.cmpc_params_default.restype = None
-    lib.cmpc_plan_create.argtypes = [ctypes.POINTER(CParams), ctypes.POINTER(vp)]
-    lib.cmpc_plan_create.restype = ctypes.c_int
-    lib.cmpc_solve.argtypes = [vp, ctypes.c_int64] + [vp] * 10
-    lib.cmpc_solve.restype = ctypes.c_int
-    if hasattr(lib, "cmpc_solve_warm"):  # absent from A/B builds of older sources
-        lib.cmpc_solve_warm.argtypes = [vp, ctypes.c_int64] + [vp] * 13
-        lib.cmpc_solve_warm.restype = ctypes.c_int
-    if hasattr(lib, "cmpc_solve_ref"):
-        lib.cmpc_solve_ref.argtypes = [vp, ctypes.c_int64] + [vp] * 13
-        lib.cmpc_solve_ref.restype = ctypes.c_int
-    if hasattr(lib, "cmpc_solve_io_run"):  # absent from builds that predate per-instance terrain
-        lib.cmpc_solve_io_run.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(CSolveIO), vp]
-        lib.cmpc_solve_io_run.restype = ctypes.c_int
-    if hasattr(lib, "cmpc_kkt_run"):  # absent from builds that predate the device-side KKT check
-        lib.cmpc_kkt_run.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(CKktIO), vp]
-        lib.cmpc_kkt_run.restype = ctypes.c_int
-    if hasattr(lib, "cmpc_gain_run"):  # absent from builds that predate the feedback gain
-        lib.cmpc_gain_run.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(CGainIO), vp]
-        lib.cmpc_gain_run.restype = ctypes.c_int
-    if hasattr(lib, "cmpc_vjp_run"):  # absent from builds that predate the backward pass
-        lib.cmpc_vjp_run.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(CVjpIO), vp]
-        lib.cmpc_vjp_run.restype = ctypes.c_int
-    if hasattr(lib, "cmpc_refine_run"):  # absent from builds that predate the refinement
-        lib.cmpc_refine_run.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(CRefineIO), vp]
-        lib.cmpc_refine_run.restype = ctypes.c_int
-    lib.cmpc_build_dynamics.argtypes = [vp, ctypes.c_int64, ctypes.c_float] + [vp] * 8
-    lib.cmpc_build_dynamics.restype = ctypes.c_int
-    if hasattr(lib, "cmpc_generate_traj"):
-        lib.cmpc_generate_traj.argtypes = [vp, ctypes.c_int64, ctypes.c_double] + [vp] * 11
-        lib.cmpc_generate_traj.restype = ctypes.c_int
-    if hasattr(lib, "cmpc_leg_torque"):
-        lib.cmpc_leg_torque.argtypes = ([vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int64] +
-                                        [vp] * 12 + [ctypes.c_double, vp, vp])
-        lib.cmpc_leg_torque.restype = ctypes.c_int
-    if hasattr(lib, "cmpc_srb_step"):
-        lib.cmpc_srb_step.argtypes = ([vp, ctypes.c_int64, ctypes.c_int, ctypes.c_double] + [vp] * 5 +
-                                      [ctypes.c_int64] + [vp] * 5)
-        lib.cmpc_srb_step.restype = ctypes.c_int
-    lib.cmpc_plan_destroy.argtypes = [vp]
-    lib.cmpc_plan_destroy.restype = None
-    lib.cmpc_plan_set_timing.argtypes = [vp, ctypes.c_int]
-    lib.cmpc_plan_set_timing.restype = ctypes.c_int
-    lib.cmpc_plan_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float),
-                                          ctypes.POINTER(ctypes.c_int32)]
-    lib.cmpc_plan_timing_read.restype = ctypes.c_int
-    if hasattr(lib, "cmpc_plan_set_team"):
-        lib.cmpc_plan_set_team.argtypes = [vp, ctypes.c_int64]
-        lib.cmpc_plan_set_team.restype = ctypes.c_int
-        lib.cmpc_plan_team_batch.argtypes = [vp, ctypes.POINTER(ctypes.c_int64)]
-        lib.cmpc_plan_team_batch.restype = ctypes.c_int
-    if hasattr(lib, "cmpc_plan_set_heavy_first"):
-        lib.cmpc_plan_set_heavy_first.argtypes = [vp, ctypes.c_int64]
-        lib.cmpc_plan_set_heavy_first.restype = ctypes.c_int
-        lib.cmpc_plan_heavy_first_batch.argtypes = [vp, ctypes.POINTER(ctypes.c_int64)]
-        lib.cmpc_plan_heavy_first_batch.restype = ctypes.c_int
-    if hasattr(lib, "cmpc_plan_stats"):
-        lib.cmpc_plan_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
-        lib.cmpc_plan_stats.restype = ctypes.c_int
-    if hasattr(lib, "cmpc_plan_solve_kernel"):
-        lib.cmpc_plan_solve_kernel.argtypes = [vp, ctypes.c_int64, ctypes.c_int]
-        lib.cmpc_plan_solve_kernel.restype = ctypes.c_char_p
-    lib.cmpc_last_error.argtypes = []
-    lib.cmpc_last_error.restype = ctypes.c_char_p
-    lib.cmpc_version.argtypes = []
-    lib.cmpc_version.restype = ctypes.c_char_p
+    for name, (argtypes, restype) in PROTOTYPES.items():
+        if hasattr(lib, name):  # a build of other sources (A/B runs) may lack an entry: Plan._need
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = argtypes, restype
     if path is None:
         _lib = lib
     return lib

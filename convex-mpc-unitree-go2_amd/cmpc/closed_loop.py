@@ -5,8 +5,7 @@ ticks it calls ``traj.generate_traj`` and ``mpc.solve_QP`` (warm-started) and ho
 until the next MPC tick; MuJoCo integrates the robot.  Here one call of :meth:`ClosedLoop.tick`
 does that for B robots with no host round trip:
 
-  cmpc_generate_traj -> cmpc_build_dynamics -> cmpc_solve_warm (cmpc_solve_io_run with
-  per-robot terrain or weights) -> cmpc_srb_step (nsub substeps)
+  cmpc_generate_traj -> cmpc_build_dynamics -> cmpc_solve_io_run -> cmpc_srb_step (nsub substeps)
 
 MuJoCo and the Go2 model are absent from this image, so the plant is ``cmpc_srb_step``'s
 single-rigid-body stand-in (include/cmpc.h) and the robot quantities Pinocchio would supply are
@@ -15,14 +14,13 @@ records one tick as a HIP graph (``torch.cuda.CUDAGraph``) so that a tick is one
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Optional
 
 import numpy as np
 import torch
 
 from . import synth
-from .solver import Plan, SolverParams, _check
+from .solver import Plan, SolverParams
 
 
 def rot_zyx(rpy: torch.Tensor) -> torch.Tensor:
@@ -169,16 +167,9 @@ class ClosedLoop:
             p.gain(self.Ad, self.Bd, self.gd, self.x_solve, self.xref, self.ct, w=self.w,
                    mu=self.mu, fz_min=self.fz_min, Q=self.Q, R=self.R, out=dict(K=self.K0),
                    stream=stream)
-        sp = ctypes.c_void_p(stream.cuda_stream)
-        P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        force = self.w[:, 12 * N:]                        # U[:, 0] rows (test_MPC.py:196)
-        with torch.cuda.device(self.dev):
-            rc = p.lib.cmpc_srb_step(p._h, ctypes.c_int64(B), ctypes.c_int(self.nsub),
-                                     ctypes.c_double(self.dt / self.nsub), P(self.t), P(self.gait),
-                                     P(self.mass), P(self.I_body), P(force),
-                                     ctypes.c_int64(self.w.stride(0)), P(self.hip), P(self.x),
-                                     P(self.feet), P(self.contact), sp)
-        _check(p.lib, rc, "cmpc_srb_step")
+        # the plant reads U[:, 0] off the rows of w (test_MPC.py:196)
+        p.srb_step(self.t, self.gait, self.mass, self.I_body, self.w[:, 12 * N:], self.hip, self.x,
+                   self.feet, self.contact, self.nsub, self.dt / self.nsub, stream=stream)
         self.t.add_(self.dt)
 
     def tick(self):

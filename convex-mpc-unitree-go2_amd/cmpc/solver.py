@@ -8,6 +8,7 @@ memory and streams.
 from __future__ import annotations
 
 import ctypes
+import functools
 from dataclasses import dataclass, field, fields
 from typing import Optional
 
@@ -66,20 +67,6 @@ def _check(lib, rc: int, what: str):
         raise CmpcError(f"{what} failed ({rc}): {_lib.last_error(lib)}")
 
 
-def _dev_tensor(t: torch.Tensor, name: str, dtype, shape) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if t.device.type != "cuda":
-        raise ValueError(f"{name} must be a device (cuda/ROCm) tensor")
-    if t.dtype != dtype:
-        raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
-    if not t.is_contiguous():
-        raise ValueError(f"{name} must be contiguous")
-    return t
-
-
 def _stream_ptr(stream, device) -> ctypes.c_void_p:
     """``stream`` (None: torch's current stream on ``device``) as the C-ABI's ``void*``."""
     if stream is None:
@@ -87,19 +74,93 @@ def _stream_ptr(stream, device) -> ctypes.c_void_p:
     return ctypes.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else stream)
 
 
-def _problem_spec(B, N, Ad, Bd, gd, x0, xref, contact) -> dict:
-    """name -> (tensor, dtype, shape) of the six arrays of a batch of B problems."""
-    f32 = torch.float32
-    return dict(Ad=(Ad, f32, (B, 12, 12)), Bd=(Bd, f32, (B, N, 12, 12)), gd=(gd, f32, (B, 12)),
-                x0=(x0, f32, (B, 12)), xref=(xref, f32, (B, N, 12)),
-                contact=(contact, torch.uint8, (B, 4, N)))
+# The specs: name -> (dtype, shape) of the tensors of an entry.  They depend on the sizes alone, so
+# a loop that calls with the same sizes every tick builds them once; callers do not modify them.
+_spec = functools.lru_cache(maxsize=32)
 
 
-def _instance_spec(B, mu, fz_min, Q, R) -> dict:
-    """The same of the optional per-instance values."""
+@_spec
+def _problem_spec(B, N) -> dict:
+    """The six arrays of a batch of B problems and the optional per-instance values."""
     f32 = torch.float32
-    return dict(mu=(mu, f32, (B,)), fz_min=(fz_min, f32, (B,)), Q=(Q, f32, (B, 12)),
-                R=(R, f32, (B, 12)))
+    return dict(Ad=(f32, (B, 12, 12)), Bd=(f32, (B, N, 12, 12)), gd=(f32, (B, 12)),
+                x0=(f32, (B, 12)), xref=(f32, (B, N, 12)), contact=(torch.uint8, (B, 4, N)),
+                mu=(f32, (B,)), fz_min=(f32, (B,)), Q=(f32, (B, 12)), R=(f32, (B, 12)))
+
+
+@_spec
+def _solve_spec(B, N) -> dict:
+    """Every tensor of a solve: the problem, the warm starts and dual outputs and the three
+    results."""
+    f32, i32 = torch.float32, torch.int32
+    nw, ny, nl = 24 * N, 12 * N, 52 * N
+    return dict(_problem_spec(B, N), w_init=(f32, (B, nw)), y_init=(f32, (B, ny)),
+                lam_init=(f32, (B, nl)), y_out=(f32, (B, ny)), lam_out=(f32, (B, nl)),
+                w=(f32, (B, nw)), status=(i32, (B,)), iters=(i32, (B,)))
+
+
+@_spec
+def _eval_spec(B, N) -> dict:
+    """Every input of the evaluation entries (kkt, gain, vjp, refine): the problem, the points,
+    their multipliers or held faces, dL/dw, and refine's in-place w_out / status."""
+    f32 = torch.float32
+    return dict(_problem_spec(B, N), w=(f32, (B, 24 * N)), lam=(f32, (B, 52 * N)),
+                faces=(torch.uint8, (B, N, 4)), gw=(f32, (B, 24 * N)), w_out=(f32, (B, 24 * N)),
+                status=(torch.int32, (B,)))
+
+
+@_spec
+def _dynamics_spec(B, N) -> tuple:
+    """(inputs, results) of cmpc_build_dynamics."""
+    f32, p = torch.float32, _problem_spec(B, N)
+    return (dict(mass=(f32, (B,)), inertia=(f32, (B, 3, 3)), r_feet=(f32, (B, N, 4, 3)),
+                 xref=p["xref"]), {k: p[k] for k in ("Ad", "Bd", "gd")})
+
+
+@_spec
+def _traj_spec(B, N) -> tuple:
+    """(inputs, results) of cmpc_generate_traj."""
+    f32, f64, p = torch.float32, torch.float64, _problem_spec(B, N)
+    return (dict(x0=p["x0"], pos_des=(f64, (B, 3)), cmd=(f32, (B, 4)), t_now=(f64, (B,)),
+                 gait=(f64, (B, 6)), foot_lever=(f32, (B, 4, 3)), hip=(f32, (4, 3))),
+            dict(xref=p["xref"], contact=p["contact"], r_feet=(f32, (B, N, 4, 3))))
+
+
+@_spec
+def _leg_spec(B) -> tuple:
+    """(inputs, results) of cmpc_leg_torque, ``force`` apart (_force_rows)."""
+    f64 = torch.float64
+    return (dict(t=(f64, (B,)), gait=(f64, (B, 6)), J_foot=(f64, (B, 4, 3, 3)),
+                 J_full=(f64, (B, 4, 3, 18)), M=(f64, (B, 18, 18)), C=(f64, (B, 18, 18)),
+                 g=(f64, (B, 18)), dq=(f64, (B, 18)), Jdot_dq=(f64, (B, 4, 3)),
+                 foot_pos=(f64, (B, 4, 3)), foot_vel=(f64, (B, 4, 3)), body=(f64, (B, 16)),
+                 hip=(f64, (4, 3)), state=(f64, (B, 4, 8))), dict(tau=(f64, (B, 12))))
+
+
+@_spec
+def _srb_spec(B) -> tuple:
+    """(inputs, results) of cmpc_srb_step, ``force`` apart: x, feet and contact_state are
+    updated in place and there is no result."""
+    f32, f64 = torch.float32, torch.float64
+    return (dict(t_now=(f64, (B,)), gait=(f64, (B, 6)), mass=(f32, (B,)),
+                 inertia_body=(f32, (B, 3, 3)), hip=(f32, (4, 3)), x=(f32, (B, 12)),
+                 feet=(f32, (B, 4, 3)), contact_state=(torch.uint8, (B,))), {})
+
+
+def _problem(Ad, Bd, gd, x0, xref, contact, **more) -> dict:
+    """name -> tensor of the six problem arrays and what else an entry requires."""
+    return dict(Ad=Ad, Bd=Bd, gd=gd, x0=x0, xref=xref, contact=contact, **more)
+
+
+def _force_rows(force, B, device) -> torch.Tensor:
+    """The one strided argument of the pipeline entries: forces as (B, 12) fp32 or a (B, >=12)
+    fp32 view whose rows start at U[:, 0] (e.g. w[:, 12N:]); its row stride goes with it."""
+    if (not isinstance(force, torch.Tensor) or force.device != device or
+            force.dtype != torch.float32 or force.dim() != 2 or force.shape[0] != B or
+            force.shape[1] < 12 or force.stride(1) != 1):
+        raise ValueError("force must be a (B, >=12) fp32 tensor on the plan's device with unit "
+                         "column stride")
+    return force
 
 
 class Plan:
@@ -121,11 +182,8 @@ class Plan:
             d = _lib.CParams()
             self.lib.cmpc_params_default(ctypes.byref(d))
             if d.abi_version != _lib.ABI_VERSION:
-                if d.abi_version not in _lib.ABI_COMPAT:
-                    raise CmpcError(f"cmpc: library ABI {d.abi_version}, this binding is ABI "
-                                    f"{_lib.ABI_VERSION} (an ABI-5 A/B build loads with "
-                                    f"CMPC_ALLOW_ABI5=1)")
-                cp.abi_version = d.abi_version   # (A/B experiments only: same layout and kernels)
+                raise CmpcError(f"cmpc: library ABI {d.abi_version}, this binding is ABI "
+                                f"{_lib.ABI_VERSION}")
             _check(self.lib, self.lib.cmpc_plan_create(ctypes.byref(cp), ctypes.byref(h)),
                    "cmpc_plan_create")
         self._h = h
@@ -141,22 +199,33 @@ class Plan:
         except Exception:
             pass
 
-    def _same_device(self, t: torch.Tensor):
-        """The plan's workspace and streams live on self.device: every tensor must too."""
+    def _address(self, t, name: str, dtype, shape) -> int:
+        """The address of tensor ``t`` once it is what the spec says: of that dtype and shape,
+        contiguous, and on the plan's device (where its workspace and streams live)."""
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
         if t.device != self.device:
-            raise ValueError(f"cmpc: tensors are on {t.device} but the plan was created on "
+            if t.device.type != "cuda":
+                raise ValueError(f"{name} must be a device (cuda/ROCm) tensor")
+            raise ValueError(f"cmpc: {name} is on {t.device} but the plan was created on "
                              f"{self.device}")
+        if t.dtype != dtype:
+            raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
+        if t.shape != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        return t.data_ptr()
 
-    def _fill_io(self, io, required: dict, optional: dict):
-        """Check the name -> (tensor, dtype, shape) specs, in their order, and point io's fields
-        of those names at the tensors; an optional tensor that is None is skipped (NULL)."""
-        for spec, skip_none in ((required, False), (optional, True)):
-            for name, (t, dtype, shape) in spec.items():
-                if t is None and skip_none:
-                    continue
-                _dev_tensor(t, name, dtype, shape)
-                self._same_device(t)
-                setattr(io, name, t.data_ptr())
+    def _fill_io(self, io, spec: dict, required: dict, optional: dict, fields: dict = {}):
+        """Check required's and optional's name -> tensor against spec's name -> (dtype, shape), in
+        their order, and point io's fields of those names (``fields``: name -> field where the
+        two differ) at them; an optional tensor that is None is skipped (NULL)."""
+        for name, t in required.items():
+            setattr(io, fields.get(name, name), self._address(t, name, *spec[name]))
+        for name, t in optional.items():
+            if t is not None:
+                setattr(io, name, self._address(t, name, *spec[name]))
 
     def _need(self, entry: str, method: str):
         """An evaluation entry that a library built from older sources does not have."""
@@ -175,11 +244,35 @@ class Plan:
             t = out.get(name)
             if t is None:
                 t = torch.empty(shape, dtype=dtype, device=device)
-            _dev_tensor(t, name, dtype, shape)
-            self._same_device(t)
-            setattr(io, field, t.data_ptr())
+            setattr(io, field, self._address(t, name, dtype, shape))
             res[name] = t
         return res
+
+    def _run_io(self, entry: str, io, B: int, stream):
+        """Call a struct entry on the plan's device; a failure raises with the library's message."""
+        with torch.cuda.device(self.device):
+            rc = getattr(self.lib, entry)(self._h, B, ctypes.byref(io),
+                                          _stream_ptr(stream, self.device))
+        _check(self.lib, rc, entry)
+
+    def _pipeline(self, entry, spec, tensors, out, stream, args) -> tuple:
+        """A pipeline entry's wrapper.  ``spec`` is (inputs, results), each name -> (dtype, shape):
+        check ``tensors`` as the inputs; take the results from the tuple ``out`` or allocate them,
+        and check them the same way; call ``entry`` with the plan, ``args(addresses of the inputs,
+        then of the results)`` and the stream.  Returns the results."""
+        self._need(entry, entry[len("cmpc_"):])
+        inputs, results = spec
+        if out is None:
+            out = tuple(torch.empty(shape, dtype=dtype, device=self.device)
+                        for dtype, shape in results.values())
+        elif len(out) != len(results):
+            raise ValueError(f"out must hold {tuple(results)}")
+        ptrs = [self._address(t, name, *inputs[name]) for name, t in zip(inputs, tensors)]
+        ptrs += [self._address(t, name, *results[name]) for name, t in zip(results, out)]
+        with torch.cuda.device(self.device):
+            rc = getattr(self.lib, entry)(self._h, *args(*ptrs), _stream_ptr(stream, self.device))
+        _check(self.lib, rc, entry)
+        return tuple(out)
 
     def set_timing(self, enable: bool):
         _check(self.lib, self.lib.cmpc_plan_set_timing(self._h, int(bool(enable))),
@@ -215,8 +308,6 @@ class Plan:
     def solve_kernels(self, B: int) -> list:
         """Names of the solve kernels a batch of B launches, per timing slot (None: slot not
         launched), as cmpc_plan_solve_kernel reports them."""
-        if not hasattr(self.lib, "cmpc_plan_solve_kernel"):  # (older A/B builds)
-            return [None] * _lib.NUM_SOLVE_KERNELS
         out = []
         for k in range(_lib.NUM_SOLVE_KERNELS):
             r = self.lib.cmpc_plan_solve_kernel(self._h, int(B), k)
@@ -227,22 +318,19 @@ class Plan:
         """Acceptance statistics since plan creation or the last reset (cmpc_plan_stats):
         loose acceptances and the answers returned as status 2 by the certified bound or a
         stalled downdated refinement.  Synchronises the device."""
-        keys = ("loose", "status2_cert", "guard_refactors", "reserved")
-        if not hasattr(self.lib, "cmpc_plan_stats"):  # (ABI-5 A/B builds)
-            return {k: None for k in keys[:3]}
+        keys = ("loose", "status2_cert", "guard_refactors")
         v = (ctypes.c_uint64 * _lib.NUM_STATS)()
         _check(self.lib, self.lib.cmpc_plan_stats(self._h, v, int(bool(reset))), "cmpc_plan_stats")
-        return {k: int(x) for k, x in zip(keys[:3], list(v))}
+        return {k: int(x) for k, x in zip(keys, list(v))}
 
     def timing_read(self):
         """-> (ms_per_kernel, calls_per_kernel) of the solve kernels since the last read, one
         entry per timing slot (_lib.KERNEL_BINS: 0 = NC 128 + 96, 1 = NC 160 + 144, 2 = NC 192)."""
-        ms = (ctypes.c_float * 4)()       # room for the round-1 ABI's four slots (A/B builds)
-        calls = (ctypes.c_int32 * 4)()
+        ms = (ctypes.c_float * _lib.NUM_SOLVE_KERNELS)()
+        calls = (ctypes.c_int32 * _lib.NUM_SOLVE_KERNELS)()
         _check(self.lib, self.lib.cmpc_plan_timing_read(self._h, ms, calls),
                "cmpc_plan_timing_read")
-        k = _lib.NUM_SOLVE_KERNELS
-        return list(ms)[:k], list(calls)[:k]
+        return list(ms), list(calls)
 
     def solve(self, Ad, Bd, gd, x0, xref, contact, out=None, stream=None, w_init=None,
               y_init=None, y_out=None, lam_init=None, lam_out=None, mu=None, fz_min=None,
@@ -250,132 +338,56 @@ class Plan:
         """Solve B instances; all inputs are device tensors (layouts: include/cmpc.h).
 
         Returns (w (B, 24N) fp32, status (B,) int32, iters (B,) int32).  Asynchronous on
-        ``stream`` (default: torch's current stream).
+        ``stream`` (default: torch's current stream).  Every option goes through one entry,
+        cmpc_solve_io_run (include/cmpc.h).
 
-        Warm start (cmpc_solve_warm; the reference's x0 / lam_x0 warm start,
+        Warm start (the reference's x0 / lam_x0 warm start,
         centroidal_mpc.py:91-95): ``w_init`` (B, 24N) a previous w, ``y_init`` (B, 12N) a
         previous dual.  ``y_out`` (B, 12N) receives the dual at the returned forces; pass
         ``y_out=True`` to allocate it, in which case the return is (w, status, iters, y).
 
-        Reference multipliers (cmpc_solve_ref; centroidal_mpc.py:91-95, 108-110):
+        Reference multipliers (centroidal_mpc.py:91-95, 108-110):
         ``lam_init`` (B, 52N) warm duals [lam_x | lam_a] in CasADi's layout and convention,
         ``lam_out`` (B, 52N) the multipliers of the returned point (``lam_out=True``
         allocates it; the return is then (w, status, iters, lam)).  Not combinable with
         y_init / y_out.
 
-        Per-instance terrain (cmpc_solve_io_run): ``mu`` (B,) the friction coefficient and
+        Per-instance terrain: ``mu`` (B,) the friction coefficient and
         ``fz_min`` (B,) the stance normal-force floor of each instance, fp32 device tensors;
         None takes the plan's constant.  They combine with every option above.  The kernels
         read them when they run, so a captured graph sees values written in place since.  An
         instance whose entry is invalid (mu not finite or <= 0, fz_min not finite) returns
         status -10 with zero forces; the others are unaffected.
 
-        Per-instance cost weights (the same entry): ``Q`` (B, 12) the state-weight diagonal and
+        Per-instance cost weights: ``Q`` (B, 12) the state-weight diagonal and
         ``R`` (B, 12) the input-weight diagonal of each instance, fp32 device tensors in the
         order of ``SolverParams.Q`` / ``R``; None takes the plan's constants.  Same rules: read
         when the kernels run, combinable with every option, and a row with a Q entry negative
         or not finite or an R entry <= 0 or not finite returns status -10 with zero forces."""
-        N = self.params.N
+        self._need("cmpc_solve_io_run", "solve")
         B = Ad.shape[0]
-        f32 = torch.float32
-        for name, spec in _problem_spec(B, N, Ad, Bd, gd, x0, xref, contact).items():
-            _dev_tensor(spec[0], name, *spec[1:])
-        self._same_device(Ad)
-        for t in (Bd, gd, x0, xref, contact):
-            if t.device != Ad.device:
-                raise ValueError("all inputs must be on the same device")
-        if out is None:
-            w = torch.empty((B, 24 * N), dtype=f32, device=Ad.device)
-            status = torch.empty((B,), dtype=torch.int32, device=Ad.device)
-            iters = torch.empty((B,), dtype=torch.int32, device=Ad.device)
-        else:
-            w, status, iters = out
-            _dev_tensor(w, "w", f32, (B, 24 * N))
-            _dev_tensor(status, "status", torch.int32, (B,))
-            _dev_tensor(iters, "iters", torch.int32, (B,))
-        sp = _stream_ptr(stream, Ad.device)
-        if mu is not None or fz_min is not None or Q is not None or R is not None:
-            return self._solve_io(B, (Ad, Bd, gd, x0, xref, contact), (w, status, iters), sp,
-                                  w_init, y_init, y_out, lam_init, lam_out, mu, fz_min, Q, R)
-        if lam_init is not None or lam_out is not None:
-            if y_init is not None or y_out is not None:
-                raise ValueError("lam_init/lam_out (reference layout) and y_init/y_out "
-                                 "(cmpc layout) are exclusive")
-            ret_l = lam_out is True
-            if ret_l:
-                lam_out = torch.empty((B, 52 * N), dtype=f32, device=Ad.device)
-            for t, name, shape in ((w_init, "w_init", (B, 24 * N)), (lam_init, "lam_init", (B, 52 * N)),
-                                   (lam_out, "lam_out", (B, 52 * N))):
-                if t is not None:
-                    _dev_tensor(t, name, f32, shape)
-                    self._same_device(t)
-            pt = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)  # noqa: E731
-            with torch.cuda.device(Ad.device):
-                rc = self.lib.cmpc_solve_ref(
-                    self._h, ctypes.c_int64(B),
-                    *[pt(t) for t in (Ad, Bd, gd, x0, xref, contact, w_init, lam_init, w, lam_out,
-                                      status, iters)], sp)
-            _check(self.lib, rc, "cmpc_solve_ref")
-            return (w, status, iters, lam_out) if ret_l else (w, status, iters)
-        ret_y = y_out is True
-        if ret_y:
-            y_out = torch.empty((B, 12 * N), dtype=f32, device=Ad.device)
-        if w_init is None and y_init is None and y_out is None:
-            with torch.cuda.device(Ad.device):
-                rc = self.lib.cmpc_solve(self._h, ctypes.c_int64(B),
-                                         *[ctypes.c_void_p(t.data_ptr()) for t in
-                                           (Ad, Bd, gd, x0, xref, contact, w, status, iters)], sp)
-            _check(self.lib, rc, "cmpc_solve")
-            return w, status, iters
-        for t, name, shape in ((w_init, "w_init", (B, 24 * N)), (y_init, "y_init", (B, 12 * N)),
-                               (y_out, "y_out", (B, 12 * N))):
-            if t is not None:
-                _dev_tensor(t, name, f32, shape)
-                if t.device != Ad.device:
-                    raise ValueError("all inputs must be on the same device")
+        spec = _solve_spec(B, self.params.N)
 
-        def ptr(t):
-            return ctypes.c_void_p(t.data_ptr() if t is not None else None)
-        with torch.cuda.device(Ad.device):
-            rc = self.lib.cmpc_solve_warm(
-                self._h, ctypes.c_int64(B),
-                *[ptr(t) for t in (Ad, Bd, gd, x0, xref, contact, w_init, y_init, w, y_out,
-                                   status, iters)], sp)
-        _check(self.lib, rc, "cmpc_solve_warm")
+        def empty(name):
+            dtype, shape = spec[name]
+            return torch.empty(shape, dtype=dtype, device=self.device)
+        ret_y, ret_l = y_out is True, lam_out is True
         if ret_y:
-            return w, status, iters, y_out
-        return w, status, iters
-
-    def _solve_io(self, B, inputs, outs, sp, w_init, y_init, y_out, lam_init, lam_out, mu, fz_min,
-                  Q=None, R=None):
-        """solve() with per-instance mu / fz_min / Q / R: the struct entry cmpc_solve_io_run."""
-        if not hasattr(self.lib, "cmpc_solve_io_run"):
-            raise CmpcError("cmpc: this libcmpc.so has no cmpc_solve_io_run: per-instance mu / "
-                            "fz_min / Q / R need a library built from sources that declare it")
+            y_out = empty("y_out")
+        if ret_l:
+            lam_out = empty("lam_out")
         if (lam_init is not None or lam_out is not None) and (y_init is not None or y_out is not None):
             raise ValueError("lam_init/lam_out (reference layout) and y_init/y_out "
                              "(cmpc layout) are exclusive")
-        N = self.params.N
-        f32 = torch.float32
-        dev = inputs[0].device
-        ret_y, ret_l = y_out is True, lam_out is True
-        if ret_y:
-            y_out = torch.empty((B, 12 * N), dtype=f32, device=dev)
-        if ret_l:
-            lam_out = torch.empty((B, 52 * N), dtype=f32, device=dev)
+        w, status, iters = (empty("w"), empty("status"), empty("iters")) if out is None else out
         io = _lib.CSolveIO()
         io.size = ctypes.sizeof(_lib.CSolveIO)
-        self._fill_io(io, _problem_spec(B, N, *inputs),
-                      dict(_instance_spec(B, mu, fz_min, Q, R),
-                           w_init=(w_init, f32, (B, 24 * N)), y_init=(y_init, f32, (B, 12 * N)),
-                           lam_init=(lam_init, f32, (B, 52 * N)), y_out=(y_out, f32, (B, 12 * N)),
-                           lam_out=(lam_out, f32, (B, 52 * N))))
-        for name, t in zip(("w_out", "status", "iters"), outs):
-            setattr(io, name, t.data_ptr())
-        with torch.cuda.device(dev):
-            rc = self.lib.cmpc_solve_io_run(self._h, ctypes.c_int64(B), ctypes.byref(io), sp)
-        _check(self.lib, rc, "cmpc_solve_io_run")
-        return outs + ((y_out,) if ret_y else ()) + ((lam_out,) if ret_l else ())
+        self._fill_io(io, spec,
+                      _problem(Ad, Bd, gd, x0, xref, contact, w=w, status=status, iters=iters),
+                      dict(w_init=w_init, y_init=y_init, lam_init=lam_init, y_out=y_out,
+                           lam_out=lam_out, mu=mu, fz_min=fz_min, Q=Q, R=R), {"w": "w_out"})
+        self._run_io("cmpc_solve_io_run", io, B, stream)
+        return (w, status, iters) + ((y_out,) if ret_y else ()) + ((lam_out,) if ret_l else ())
 
     def kkt(self, Ad, Bd, gd, x0, xref, contact, w, lam=None, mu=None, fz_min=None, Q=None,
             R=None, face_tol=None, out=None, stream=None):
@@ -397,22 +409,15 @@ class Plan:
         B = Ad.shape[0]
         if B < 1:
             raise ValueError("kkt needs at least one instance")
-        f32 = torch.float32
         io = _lib.CKktIO()
         io.size = ctypes.sizeof(_lib.CKktIO)
-        self._fill_io(io, dict(_problem_spec(B, N, Ad, Bd, gd, x0, xref, contact),
-                               w=(w, f32, (B, 24 * N))),
-                      dict(lam=(lam, f32, (B, 52 * N)), **_instance_spec(B, mu, fz_min, Q, R)))
+        self._fill_io(io, _eval_spec(B, N), _problem(Ad, Bd, gd, x0, xref, contact, w=w),
+                      dict(lam=lam, mu=mu, fz_min=fz_min, Q=Q, R=R))
         if out is None:
-            out = torch.empty((B, 4), dtype=torch.float64, device=Ad.device)
-        _dev_tensor(out, "out", torch.float64, (B, 4))
-        self._same_device(out)
-        io.res = out.data_ptr()
+            out = torch.empty((B, 4), dtype=torch.float64, device=self.device)
+        io.res = self._address(out, "out", torch.float64, (B, 4))
         io.face_tol = 0.0 if face_tol is None else float(face_tol)
-        sp = _stream_ptr(stream, Ad.device)
-        with torch.cuda.device(Ad.device):
-            rc = self.lib.cmpc_kkt_run(self._h, ctypes.c_int64(B), ctypes.byref(io), sp)
-        _check(self.lib, rc, "cmpc_kkt_run")
+        self._run_io("cmpc_kkt_run", io, B, stream)
         return out
 
     def gain(self, Ad, Bd, gd, x0, xref, contact, w=None, faces=None, mu=None, fz_min=None,
@@ -444,20 +449,16 @@ class Plan:
         B = Ad.shape[0]
         if B < 1:
             raise ValueError("gain needs at least one instance")
-        f32, f64, u8 = torch.float32, torch.float64, torch.uint8
+        f64, u8 = torch.float64, torch.uint8
         io = _lib.CGainIO()
         io.size = ctypes.sizeof(_lib.CGainIO)
-        self._fill_io(io, _problem_spec(B, N, Ad, Bd, gd, x0, xref, contact),
-                      dict(w=(w, f32, (B, 24 * N)), faces=(faces, u8, (B, N, 4)),
-                           **_instance_spec(B, mu, fz_min, Q, R)))
+        self._fill_io(io, _eval_spec(B, N), _problem(Ad, Bd, gd, x0, xref, contact),
+                      dict(w=w, faces=faces, mu=mu, fz_min=fz_min, Q=Q, R=R))
         spec = dict(K=("K", f64, (B, 12, 12)), Vx=("Vx", f64, (B, 12)), Vxx=("Vxx", f64, (B, 12, 12)),
                     u_star=("u_star", f64, (B, 12 * N)), faces=("faces_out", u8, (B, N, 4)))
-        res = self._results(io, spec, want, ("K",), out, Ad.device)
+        res = self._results(io, spec, want, ("K",), out, self.device)
         io.face_tol = 0.0 if face_tol is None else float(face_tol)
-        sp = _stream_ptr(stream, Ad.device)
-        with torch.cuda.device(Ad.device):
-            rc = self.lib.cmpc_gain_run(self._h, ctypes.c_int64(B), ctypes.byref(io), sp)
-        _check(self.lib, rc, "cmpc_gain_run")
+        self._run_io("cmpc_gain_run", io, B, stream)
         return res
 
     def vjp(self, Ad, Bd, gd, x0, xref, contact, gw, w=None, faces=None, mu=None, fz_min=None,
@@ -489,22 +490,17 @@ class Plan:
         B = Ad.shape[0]
         if B < 1:
             raise ValueError("vjp needs at least one instance")
-        f32, f64, u8 = torch.float32, torch.float64, torch.uint8
+        f64 = torch.float64
         io = _lib.CVjpIO()
         io.size = ctypes.sizeof(_lib.CVjpIO)
-        self._fill_io(io, dict(_problem_spec(B, N, Ad, Bd, gd, x0, xref, contact),
-                               gw=(gw, f32, (B, 24 * N))),
-                      dict(w=(w, f32, (B, 24 * N)), faces=(faces, u8, (B, N, 4)),
-                           **_instance_spec(B, mu, fz_min, Q, R)))
+        self._fill_io(io, _eval_spec(B, N), _problem(Ad, Bd, gd, x0, xref, contact, gw=gw),
+                      dict(w=w, faces=faces, mu=mu, fz_min=fz_min, Q=Q, R=R))
         shapes = dict(x0=(B, 12), xref=(B, N, 12), gd=(B, 12), Q=(B, 12), R=(B, 12), mu=(B,),
                       fz_min=(B,), Ad=(B, 12, 12), Bd=(B, N, 12, 12))
         spec = {name: ("g_" + name, f64, shape) for name, shape in shapes.items()}
-        res = self._results(io, spec, want, (), out, Ad.device)
+        res = self._results(io, spec, want, (), out, self.device)
         io.face_tol = 0.0 if face_tol is None else float(face_tol)
-        sp = _stream_ptr(stream, Ad.device)
-        with torch.cuda.device(Ad.device):
-            rc = self.lib.cmpc_vjp_run(self._h, ctypes.c_int64(B), ctypes.byref(io), sp)
-        _check(self.lib, rc, "cmpc_vjp_run")
+        self._run_io("cmpc_vjp_run", io, B, stream)
         return res
 
     def refine(self, Ad, Bd, gd, x0, xref, contact, w=None, faces=None, mu=None, fz_min=None,
@@ -545,24 +541,20 @@ class Plan:
         B = Ad.shape[0]
         if B < 1:
             raise ValueError("refine needs at least one instance")
-        f32, f64, u8, i32 = torch.float32, torch.float64, torch.uint8, torch.int32
+        f64, u8, i32 = torch.float64, torch.uint8, torch.int32
         io = _lib.CRefineIO()
         io.size = ctypes.sizeof(_lib.CRefineIO)
-        self._fill_io(io, _problem_spec(B, N, Ad, Bd, gd, x0, xref, contact),
-                      dict(w=(w, f32, (B, 24 * N)), faces=(faces, u8, (B, N, 4)),
-                           w_out=(w_out, f32, (B, 24 * N)), status=(status, i32, (B,)),
-                           **_instance_spec(B, mu, fz_min, Q, R)))
+        self._fill_io(io, _eval_spec(B, N), _problem(Ad, Bd, gd, x0, xref, contact),
+                      dict(w=w, faces=faces, w_out=w_out, status=status, mu=mu, fz_min=fz_min,
+                           Q=Q, R=R))
         spec = dict(info=("info", i32, (B,)), res=("res", f64, (B, 3)),
                     w64=("w64", f64, (B, 24 * N)), lam=("lam_out", f64, (B, 52 * N)),
                     faces=("faces_out", u8, (B, N, 4)))
-        res = self._results(io, spec, want, ("info",), out, Ad.device)
+        res = self._results(io, spec, want, ("info",), out, self.device)
         io.face_tol = float(face_tol)
         io.max_rounds = int(max_rounds)
         io.prim_tol, io.dual_tol = float(prim_tol), float(dual_tol)
-        sp = _stream_ptr(stream, Ad.device)
-        with torch.cuda.device(Ad.device):
-            rc = self.lib.cmpc_refine_run(self._h, ctypes.c_int64(B), ctypes.byref(io), sp)
-        _check(self.lib, rc, "cmpc_refine_run")
+        self._run_io("cmpc_refine_run", io, B, stream)
         return res
 
     def build_dynamics(self, mass, inertia, r_feet, xref, dt, out=None, stream=None):
@@ -570,35 +562,9 @@ class Plan:
         ComTraj._continuousDynamics + _discreteDynamics (com_trajectory.py:221-286) in closed
         form.  mass (B,), inertia (B,3,3) I_com_world, r_feet (B,N,4,3) COM->foot lever arms
         (legs FL FR RL RR), xref (B,N,12) as for solve(); all fp32 device tensors."""
-        N = self.params.N
         B = mass.shape[0]
-        f32 = torch.float32
-        _dev_tensor(mass, "mass", f32, (B,))
-        _dev_tensor(inertia, "inertia", f32, (B, 3, 3))
-        _dev_tensor(r_feet, "r_feet", f32, (B, N, 4, 3))
-        _dev_tensor(xref, "xref", f32, (B, N, 12))
-        self._same_device(mass)
-        for t in (inertia, r_feet, xref):
-            if t.device != mass.device:
-                raise ValueError("all inputs must be on the same device")
-        if out is None:
-            Ad = torch.empty((B, 12, 12), dtype=f32, device=mass.device)
-            Bd = torch.empty((B, N, 12, 12), dtype=f32, device=mass.device)
-            gd = torch.empty((B, 12), dtype=f32, device=mass.device)
-        else:
-            Ad, Bd, gd = out
-            _dev_tensor(Ad, "Ad", f32, (B, 12, 12))
-            _dev_tensor(Bd, "Bd", f32, (B, N, 12, 12))
-            _dev_tensor(gd, "gd", f32, (B, 12))
-        sp = _stream_ptr(stream, mass.device)
-        with torch.cuda.device(mass.device):
-            rc = self.lib.cmpc_build_dynamics(
-                self._h, ctypes.c_int64(B), ctypes.c_float(dt),
-                *[ctypes.c_void_p(t.data_ptr()) for t in (mass, inertia, r_feet, xref, Ad, Bd, gd)],
-                sp)
-        _check(self.lib, rc, "cmpc_build_dynamics")
-        return Ad, Bd, gd
-
+        return self._pipeline("cmpc_build_dynamics", _dynamics_spec(B, self.params.N),
+                              (mass, inertia, r_feet, xref), out, stream, lambda *p: (B, dt, *p))
 
     def generate_traj(self, x0, pos_des, cmd, t_now, gait, foot_lever, hip, dt, out=None,
                       stream=None):
@@ -609,39 +575,10 @@ class Plan:
         t_now (B,) fp64; gait (B,6) fp64 [period, duty, 4 phase offsets]; foot_lever (B,4,3)
         fp32; hip (4,3) fp32.  Returns (xref (B,N,12), contact (B,4,N) uint8,
         r_feet (B,N,4,3))."""
-        N = self.params.N
         B = x0.shape[0]
-        f32, f64 = torch.float32, torch.float64
-        _dev_tensor(x0, "x0", f32, (B, 12))
-        _dev_tensor(pos_des, "pos_des", f64, (B, 3))
-        _dev_tensor(cmd, "cmd", f32, (B, 4))
-        _dev_tensor(t_now, "t_now", f64, (B,))
-        _dev_tensor(gait, "gait", f64, (B, 6))
-        _dev_tensor(foot_lever, "foot_lever", f32, (B, 4, 3))
-        _dev_tensor(hip, "hip", f32, (4, 3))
-        self._same_device(x0)
-        for t in (pos_des, cmd, t_now, gait, foot_lever, hip):
-            if t.device != x0.device:
-                raise ValueError("all inputs must be on the same device")
-        if out is None:
-            xref = torch.empty((B, N, 12), dtype=f32, device=x0.device)
-            contact = torch.empty((B, 4, N), dtype=torch.uint8, device=x0.device)
-            r_feet = torch.empty((B, N, 4, 3), dtype=f32, device=x0.device)
-        else:
-            xref, contact, r_feet = out
-            _dev_tensor(xref, "xref", f32, (B, N, 12))
-            _dev_tensor(contact, "contact", torch.uint8, (B, 4, N))
-            _dev_tensor(r_feet, "r_feet", f32, (B, N, 4, 3))
-        sp = _stream_ptr(stream, x0.device)
-        with torch.cuda.device(x0.device):
-            rc = self.lib.cmpc_generate_traj(
-                self._h, ctypes.c_int64(B), ctypes.c_double(dt),
-                *[ctypes.c_void_p(t.data_ptr()) for t in (x0, pos_des, cmd, t_now, gait,
-                                                          foot_lever, hip, xref, contact, r_feet)],
-                sp)
-        _check(self.lib, rc, "cmpc_generate_traj")
-        return xref, contact, r_feet
-
+        return self._pipeline("cmpc_generate_traj", _traj_spec(B, self.params.N),
+                              (x0, pos_des, cmd, t_now, gait, foot_lever, hip), out, stream,
+                              lambda *p: (B, dt, *p))
 
     def leg_torque(self, t, gait, force, J_foot, J_full, M, C, g, dq, Jdot_dq, foot_pos, foot_vel,
                    body, hip, state, tau_max=45.0, out=None, stream=None):
@@ -651,36 +588,27 @@ class Plan:
         fp64 device tensors; ``state`` (B, 4, 8) is updated in place (initialise with
         :func:`leg_state`).  Returns tau (B, 12) fp64."""
         B = t.shape[0]
-        f64 = torch.float64
-        _dev_tensor(t, "t", f64, (B,))
-        _dev_tensor(gait, "gait", f64, (B, 6))
-        if (not isinstance(force, torch.Tensor) or force.device.type != "cuda" or
-                force.dtype != torch.float32 or force.dim() != 2 or force.shape[0] != B or
-                force.shape[1] < 12 or force.stride(1) != 1):
-            raise ValueError("force must be a (B, >=12) fp32 device tensor with unit column stride")
-        for name, x, shp in (("J_foot", J_foot, (B, 4, 3, 3)), ("J_full", J_full, (B, 4, 3, 18)),
-                             ("M", M, (B, 18, 18)), ("C", C, (B, 18, 18)), ("g", g, (B, 18)),
-                             ("dq", dq, (B, 18)), ("Jdot_dq", Jdot_dq, (B, 4, 3)),
-                             ("foot_pos", foot_pos, (B, 4, 3)), ("foot_vel", foot_vel, (B, 4, 3)),
-                             ("body", body, (B, 16)), ("hip", hip, (4, 3)),
-                             ("state", state, (B, 4, 8))):
-            _dev_tensor(x, name, f64, shp)
-        for x in (t, gait, force, J_foot, J_full, M, C, g, dq, Jdot_dq, foot_pos, foot_vel, body,
-                  hip, state):
-            self._same_device(x)
-        tau = torch.empty((B, 12), dtype=f64, device=t.device) if out is None else out
-        _dev_tensor(tau, "tau", f64, (B, 12))
-        sp = _stream_ptr(stream, t.device)
-        P = lambda x: ctypes.c_void_p(x.data_ptr())  # noqa: E731
-        with torch.cuda.device(t.device):
-            rc = self.lib.cmpc_leg_torque(
-                self._h, ctypes.c_int64(B), P(t), P(gait), P(force),
-                ctypes.c_int64(force.stride(0)), *[P(x) for x in (J_foot, J_full, M, C, g, dq,
-                                                               Jdot_dq, foot_pos, foot_vel, body,
-                                                               hip, state)],
-                ctypes.c_double(tau_max), P(tau), sp)
-        _check(self.lib, rc, "cmpc_leg_torque")
-        return tau
+        _force_rows(force, B, self.device)
+        return self._pipeline(
+            "cmpc_leg_torque", _leg_spec(B),
+            (t, gait, J_foot, J_full, M, C, g, dq, Jdot_dq, foot_pos, foot_vel, body, hip, state),
+            None if out is None else (out,), stream,
+            lambda t_, gait_, *p: (B, t_, gait_, force.data_ptr(), force.stride(0), *p[:12],
+                                   tau_max, p[12]))[0]
+
+    def srb_step(self, t_now, gait, mass, inertia_body, force, hip, x, feet, contact_state, nsub,
+                 dt, stream=None):
+        """``nsub`` substeps of ``dt`` of the single-rigid-body plant for B robots
+        (cmpc_srb_step, include/cmpc.h).  t_now (B,) and gait (B, 6) fp64; mass (B,),
+        inertia_body (B, 3, 3) and hip (4, 3) fp32; ``force`` as for :meth:`leg_torque`; x
+        (B, 12) fp32, feet (B, 4, 3) fp32 and contact_state (B,) uint8 are updated in place."""
+        B = x.shape[0]
+        _force_rows(force, B, self.device)
+        self._pipeline(
+            "cmpc_srb_step", _srb_spec(B),
+            (t_now, gait, mass, inertia_body, hip, x, feet, contact_state), None, stream,
+            lambda t_, gait_, mass_, inertia_, *p: (B, int(nsub), dt, t_, gait_, mass_, inertia_,
+                                                    force.data_ptr(), force.stride(0), *p))
 
 
 def leg_state(B: int, device="cuda") -> torch.Tensor:

@@ -32,10 +32,11 @@ struct cmpc_plan {
   cmpc::KParams kp;
   int device;
   int cus = 0;      // compute units of the device
-  int* d_counters;  // counts[kNumBins], heads[kNumBins]
+  int* d_counters = nullptr;  // counts[kNumBins], heads[kNumBins]
   unsigned long long* d_stats = nullptr;  // CMPC_NUM_STATS cumulative counters (cmpc_plan_stats)
-  int* d_lists;     // kNumBins * max_batch
-  float* d_work;    // per-wave park slabs; group k's region starts at work_off[k] (groups overlap)
+  int* d_lists = nullptr;     // kNumBins * max_batch
+  // per-wave park slabs; group k's region starts at work_off[k] (groups overlap)
+  float* d_work = nullptr;
   size_t work_off[kNumGroups];
   int grid[kNumGroups];      // persistent grid of each group's one-wave kernel
   size_t slab[kNumGroups];   // park slab per wave (floats)
@@ -78,6 +79,8 @@ int hip_fail(hipError_t e, const char* what) {
 
 using KernelFn = void (*)(cmpc::KParams, cmpc::Inputs, cmpc::Outputs, const int*, const int*,
                           const int*, int*, int, float*, size_t);
+using TeamFn = void (*)(cmpc::KParams, cmpc::Inputs, cmpc::Outputs, const int*, int64_t,
+                        const int*, int*, float*, size_t);
 
 // The plan's workspace, streams and events belong to the device current at cmpc_plan_create:
 // every launch must run there (the Python layer makes the tensors' device current).
@@ -183,13 +186,27 @@ unsigned grid_stride_blocks(int64_t B, int64_t cap = 8192) {
   return (unsigned)std::min(B, cap);
 }
 
+// every kernel launch of this file: `what` names the launch in the error message
+template <class K, class... A>
+int launch(K kernel, const char* what, unsigned grid, unsigned block, size_t dyn_lds, void* stream,
+           A... args) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), dyn_lds, (hipStream_t)stream, args...);
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? hip_fail(e, what) : CMPC_OK;
+}
+
 // launch an evaluation kernel, one wave per instance, grid-stride over B
 template <class K, class... A>
 int launch_eval(K kernel, const char* what, int64_t B, size_t dyn_lds, void* stream, A... args) {
-  hipLaunchKernelGGL(kernel, dim3(grid_stride_blocks(B)), dim3(64), dyn_lds, (hipStream_t)stream,
-                     args...);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, what);
+  return launch(kernel, what, grid_stride_blocks(B), 64, dyn_lds, stream, args...);
+}
+
+// the opening checks of the pipeline entries (dynamics, trajectory, leg controller, plant)
+int check_pipeline(const cmpc_plan* pl, const char* what, bool negative,
+                   const char* msg = ": negative batch") {
+  if (!pl) return fail(CMPC_E_INVALID, std::string(what) + ": null plan");
+  if (int rc = check_device(pl, what)) return rc;
+  if (negative) return fail(CMPC_E_INVALID, std::string(what) + msg);
   return CMPC_OK;
 }
 
@@ -276,19 +293,28 @@ int cmpc_plan_create(const cmpc_params* p, cmpc_plan** out) {
   k.polish_repairs = p->polish_repairs;
   k.check_every = p->check_termination;
 
+  // every failure from here on: destroy what exists so far (cmpc_plan_destroy tolerates nulls),
+  // then set the message
+  const auto give_up = [pl](int code, const std::string& msg) {
+    cmpc_plan_destroy(pl);
+    return fail(code, msg);
+  };
+  const auto hip_give_up = [&](hipError_t err, const char* what) {
+    return give_up(CMPC_E_HIP, std::string(what) + ": " + hipGetErrorString(err));
+  };
   hipError_t e = hipGetDevice(&pl->device);
-  if (e != hipSuccess) { delete pl; return hip_fail(e, "hipGetDevice"); }
+  if (e != hipSuccess) return hip_give_up(e, "hipGetDevice");
   int cus = 0;
   e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pl->device);
   pl->cus = cus;
-  if (e != hipSuccess) { delete pl; return hip_fail(e, "hipDeviceGetAttribute"); }
+  if (e != hipSuccess) return hip_give_up(e, "hipDeviceGetAttribute");
   // persistent grids: resident workgroups per CU x CUs
   size_t work_floats = 0;
   for (int k = 0; k < kNumGroups; ++k) {
     int nb = 0;
     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, group_fn(k), 64, 0);
-    if (e != hipSuccess) { delete pl; return hip_fail(e, "hipOccupancyMaxActiveBlocksPerMultiprocessor"); }
-    if (nb < 1) { delete pl; return fail(CMPC_E_HIP, "cmpc_plan_create: solve kernel cannot be resident"); }
+    if (e != hipSuccess) return hip_give_up(e, "hipOccupancyMaxActiveBlocksPerMultiprocessor");
+    if (nb < 1) return give_up(CMPC_E_HIP, "cmpc_plan_create: solve kernel cannot be resident");
 #ifdef CMPC_STAMPS
     if (const char* cap = getenv("CMPC_BLOCKS_PER_CU")) {  // diagnostic build: occupancy sweep
       const int c = atoi(cap);
@@ -304,12 +330,12 @@ int cmpc_plan_create(const cmpc_params* p, cmpc_plan** out) {
     int nb = 0;
     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, cmpc::solve_team_kernel<kTeamWaves, 2>,
                                                      64 * kTeamWaves, 0);
-    if (e != hipSuccess) { delete pl; return hip_fail(e, "hipOccupancyMaxActiveBlocksPerMultiprocessor"); }
+    if (e != hipSuccess) return hip_give_up(e, "hipOccupancyMaxActiveBlocksPerMultiprocessor");
     if (nb < 1) nb = 1;
     pl->team_grid = nb * cus;
     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, cmpc::solve_team_kernel<kTeamWaves, 1>,
                                                      64 * kTeamWaves, 0);
-    if (e != hipSuccess) { delete pl; return hip_fail(e, "hipOccupancyMaxActiveBlocksPerMultiprocessor"); }
+    if (e != hipSuccess) return hip_give_up(e, "hipOccupancyMaxActiveBlocksPerMultiprocessor");
     // (0 if the one-per-CU image cannot be resident: team_one_per_cu then never selects it and
     // the two-per-CU image serves every team batch)
     pl->team_grid1 = nb < 1 ? 0 : cus;
@@ -317,25 +343,14 @@ int cmpc_plan_create(const cmpc_params* p, cmpc_plan** out) {
                               cmpc::TeamCfg<128, kTeamWaves>::SLAB, cmpc::TeamCfg<96, kTeamWaves>::SLAB});
     work_floats = std::max(work_floats, (size_t)pl->team_grid * pl->team_slab);
   }
-  e = hipMalloc(&pl->d_counters, 2 * cmpc::kNumBins * sizeof(int));
-  if (e != hipSuccess) { delete pl; return fail(CMPC_E_NOMEM, "hipMalloc counters failed"); }
-  e = hipMalloc(&pl->d_work, work_floats * sizeof(float));
-  if (e != hipSuccess) {
-    (void)hipFree(pl->d_counters);
-    delete pl;
-    return fail(CMPC_E_NOMEM, "hipMalloc workspace failed");
-  }
-  e = hipMalloc(&pl->d_lists, (size_t)cmpc::kNumBins * p->max_batch * sizeof(int));
-  if (e != hipSuccess) {
-    (void)hipFree(pl->d_counters);
-    (void)hipFree(pl->d_work);
-    delete pl;
-    return fail(CMPC_E_NOMEM, "hipMalloc lists failed");
-  }
-  if ((e = hipMalloc(&pl->d_stats, CMPC_NUM_STATS * sizeof(unsigned long long))) != hipSuccess) {
-    cmpc_plan_destroy(pl);
-    return fail(CMPC_E_NOMEM, "hipMalloc stats failed");
-  }
+  if (hipMalloc(&pl->d_counters, 2 * cmpc::kNumBins * sizeof(int)) != hipSuccess)
+    return give_up(CMPC_E_NOMEM, "hipMalloc counters failed");
+  if (hipMalloc(&pl->d_work, work_floats * sizeof(float)) != hipSuccess)
+    return give_up(CMPC_E_NOMEM, "hipMalloc workspace failed");
+  if (hipMalloc(&pl->d_lists, (size_t)cmpc::kNumBins * p->max_batch * sizeof(int)) != hipSuccess)
+    return give_up(CMPC_E_NOMEM, "hipMalloc lists failed");
+  if (hipMalloc(&pl->d_stats, CMPC_NUM_STATS * sizeof(unsigned long long)) != hipSuccess)
+    return give_up(CMPC_E_NOMEM, "hipMalloc stats failed");
   // the NC 192 stream at the highest priority: its few early waves are dispatched ahead of the
   // register classes submitted right after them on the other queues (solve_impl)
   int prio_lo = 0, prio_hi = 0;
@@ -344,19 +359,15 @@ int cmpc_plan_create(const cmpc_params* p, cmpc_plan** out) {
       (e = hipStreamCreateWithPriority(&pl->top, hipStreamNonBlocking, prio_hi)) != hipSuccess ||
       (e = hipEventCreateWithFlags(&pl->fork, hipEventDisableTiming)) != hipSuccess ||
       (e = hipEventCreateWithFlags(&pl->join, hipEventDisableTiming)) != hipSuccess ||
-      (e = hipEventCreateWithFlags(&pl->join_top, hipEventDisableTiming)) != hipSuccess) {
-    cmpc_plan_destroy(pl);
-    return hip_fail(e, "side stream/event creation");
-  }
+      (e = hipEventCreateWithFlags(&pl->join_top, hipEventDisableTiming)) != hipSuccess)
+    return hip_give_up(e, "side stream/event creation");
   // zeroed on the plan's own stream: a copy or memset on the null stream here (the caller's
   // default stream, round 6's first ABI-6 build) made the closed loop's HIP-graph replay at
   // 65,536 robots 1.3x slower than eager (profiles/r06l_*)
   if ((e = hipMemsetAsync(pl->d_stats, 0, CMPC_NUM_STATS * sizeof(unsigned long long), pl->side)) !=
           hipSuccess ||
-      (e = hipStreamSynchronize(pl->side)) != hipSuccess) {
-    cmpc_plan_destroy(pl);
-    return hip_fail(e, "hipMemsetAsync stats");
-  }
+      (e = hipStreamSynchronize(pl->side)) != hipSuccess)
+    return hip_give_up(e, "hipMemsetAsync stats");
   *out = pl;
   g_err.clear();
   return CMPC_OK;
@@ -365,72 +376,68 @@ int cmpc_plan_create(const cmpc_params* p, cmpc_plan** out) {
 static int solve_impl(cmpc_plan* pl, int64_t B, const cmpc::Inputs& in, const cmpc::Outputs& out,
                       void* stream);
 
-// the argument checks every solve entry shares (`what` names the entry in the message)
-static int solve_checked(cmpc_plan* pl, int64_t B, const cmpc::Inputs& in, cmpc::Outputs out,
-                         void* stream, const char* what) {
+// Every solve entry ends here with its arguments in a cmpc_solve_io (`what` names the entry in
+// the messages): the checks, then the kernels' Inputs / Outputs.
+static int solve_io(cmpc_plan* pl, int64_t B, const cmpc_solve_io& a, void* stream,
+                    const char* what) {
   const std::string w(what);
   if (!pl) return fail(CMPC_E_INVALID, w + ": null plan");
   if (B < 0) return fail(CMPC_E_INVALID, w + ": negative batch");
   if (B == 0) return CMPC_OK;
   if (B > pl->p.max_batch) return fail(CMPC_E_RANGE, w + ": B exceeds plan max_batch");
-  if (!in.Ad || !in.Bd || !in.gd || !in.x0 || !in.xref || !in.contact || !out.w || !out.status ||
-      !out.iters)
+  if (!a.Ad || !a.Bd || !a.gd || !a.x0 || !a.xref || !a.contact || !a.w_out || !a.status ||
+      !a.iters)
     return fail(CMPC_E_INVALID, w + ": null array argument");
+  cmpc::Inputs in;
+  in.Ad = a.Ad; in.Bd = a.Bd; in.gd = a.gd; in.x0 = a.x0; in.xref = a.xref;
+  in.contact = a.contact;
+  in.w_init = a.w_init; in.y_init = a.y_init; in.lam_init = a.lam_init;
+  in.mu = a.mu; in.fz_min = a.fz_min; in.Q = a.Q; in.R = a.R;
+  cmpc::Outputs out;
+  out.w = a.w_out; out.status = a.status; out.iters = a.iters;
+  out.y = a.y_out; out.lam = a.lam_out;
   out.stats = pl->d_stats;
   return solve_impl(pl, B, in, out, stream);
 }
 
-// The arrays every solve entry takes; the entries set the optional fields they pass by name
-// (the rest stay NULL).
-static cmpc::Inputs problem_inputs(const float* Ad, const float* Bd, const float* gd,
-                                   const float* x0, const float* xref, const uint8_t* contact) {
-  cmpc::Inputs in;
-  in.Ad = Ad;
-  in.Bd = Bd;
-  in.gd = gd;
-  in.x0 = x0;
-  in.xref = xref;
-  in.contact = contact;
-  return in;
-}
-
-static cmpc::Outputs solve_outputs(float* w_out, int32_t* status, int32_t* iters) {
-  cmpc::Outputs out;
-  out.w = w_out;
-  out.status = status;
-  out.iters = iters;
-  return out;
+// the arguments every positional solve entry takes, as a cmpc_solve_io with the rest NULL
+static cmpc_solve_io positional_io(const float* Ad, const float* Bd, const float* gd,
+                                   const float* x0, const float* xref, const uint8_t* contact,
+                                   const float* w_init, float* w_out, int32_t* status,
+                                   int32_t* iters) {
+  cmpc_solve_io a;
+  memset(&a, 0, sizeof(a));
+  a.size = sizeof(a);
+  a.Ad = Ad; a.Bd = Bd; a.gd = gd; a.x0 = x0; a.xref = xref; a.contact = contact;
+  a.w_init = w_init; a.w_out = w_out; a.status = status; a.iters = iters;
+  return a;
 }
 
 int cmpc_solve(cmpc_plan* pl, int64_t B, const float* Ad, const float* Bd, const float* gd,
                const float* x0, const float* xref, const uint8_t* contact, float* w_out,
                int32_t* status, int32_t* iters, void* stream) {
-  return solve_checked(pl, B, problem_inputs(Ad, Bd, gd, x0, xref, contact),
-                       solve_outputs(w_out, status, iters), stream, "cmpc_solve");
+  return solve_io(pl, B, positional_io(Ad, Bd, gd, x0, xref, contact, nullptr, w_out, status, iters),
+                  stream, "cmpc_solve");
 }
 
 int cmpc_solve_warm(cmpc_plan* pl, int64_t B, const float* Ad, const float* Bd,
                     const float* gd, const float* x0, const float* xref,
                     const uint8_t* contact, const float* w_init, const float* y_init,
                     float* w_out, float* y_out, int32_t* status, int32_t* iters, void* stream) {
-  cmpc::Inputs in = problem_inputs(Ad, Bd, gd, x0, xref, contact);
-  in.w_init = w_init;
-  in.y_init = y_init;
-  cmpc::Outputs out = solve_outputs(w_out, status, iters);
-  out.y = y_out;
-  return solve_checked(pl, B, in, out, stream, "cmpc_solve_warm");
+  cmpc_solve_io a = positional_io(Ad, Bd, gd, x0, xref, contact, w_init, w_out, status, iters);
+  a.y_init = y_init;
+  a.y_out = y_out;
+  return solve_io(pl, B, a, stream, "cmpc_solve_warm");
 }
 
 int cmpc_solve_ref(cmpc_plan* pl, int64_t B, const float* Ad, const float* Bd, const float* gd,
                    const float* x0, const float* xref, const uint8_t* contact,
                    const float* w_init, const float* lam_init, float* w_out, float* lam_out,
                    int32_t* status, int32_t* iters, void* stream) {
-  cmpc::Inputs in = problem_inputs(Ad, Bd, gd, x0, xref, contact);
-  in.w_init = w_init;
-  in.lam_init = lam_init;
-  cmpc::Outputs out = solve_outputs(w_out, status, iters);
-  out.lam = lam_out;
-  return solve_checked(pl, B, in, out, stream, "cmpc_solve_ref");
+  cmpc_solve_io a = positional_io(Ad, Bd, gd, x0, xref, contact, w_init, w_out, status, iters);
+  a.lam_init = lam_init;
+  a.lam_out = lam_out;
+  return solve_io(pl, B, a, stream, "cmpc_solve_ref");
 }
 
 int cmpc_solve_io_run(cmpc_plan* pl, int64_t B, const cmpc_solve_io* io, void* stream) {
@@ -440,18 +447,7 @@ int cmpc_solve_io_run(cmpc_plan* pl, int64_t B, const cmpc_solve_io* io, void* s
   if ((a.y_init || a.y_out) && (a.lam_init || a.lam_out))
     return fail(CMPC_E_INVALID, "cmpc_solve_io_run: y_init / y_out (this solver's dual) and "
                                 "lam_init / lam_out (the reference's multipliers) are exclusive");
-  cmpc::Inputs in = problem_inputs(a.Ad, a.Bd, a.gd, a.x0, a.xref, a.contact);
-  in.w_init = a.w_init;
-  in.y_init = a.y_init;
-  in.lam_init = a.lam_init;
-  in.mu = a.mu;
-  in.fz_min = a.fz_min;
-  in.Q = a.Q;
-  in.R = a.R;
-  cmpc::Outputs out = solve_outputs(a.w_out, a.status, a.iters);
-  out.y = a.y_out;
-  out.lam = a.lam_out;
-  return solve_checked(pl, B, in, out, stream, "cmpc_solve_io_run");
+  return solve_io(pl, B, a, stream, "cmpc_solve_io_run");
 }
 
 int cmpc_kkt_run(cmpc_plan* pl, int64_t B, const cmpc_kkt_io* io, void* stream) {
@@ -558,14 +554,12 @@ static int record_launch(cmpc_plan* pl, int k, hipStream_t s, const cmpc::KParam
   int rc = timing_begin(pl, k, s, timed, rec);
   if (rc != CMPC_OK) return rc;
   const int qa = group_first_bin(k);
-  hipLaunchKernelGGL(group_fn(k), dim3(g), dim3(64), 0, s, kp, in, out,
-                     pl->d_lists + (size_t)qa * pl->p.max_batch,
-                     pl->d_lists + (size_t)(qa - 1) * pl->p.max_batch, pl->d_counters,
-                     pl->d_counters + cmpc::kNumBins, qa,
-                     pl->d_work + pl->work_off[k] + (size_t)w0 * pl->slab[k], pl->slab[k]);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "solve_group_kernel launch");
-  return timing_end(pl, s, rec);
+  rc = launch(group_fn(k), "solve_group_kernel launch", g, 64, 0, s, kp, in, out,
+              pl->d_lists + (size_t)qa * pl->p.max_batch,
+              pl->d_lists + (size_t)(qa - 1) * pl->p.max_batch, pl->d_counters,
+              pl->d_counters + cmpc::kNumBins, qa,
+              pl->d_work + pl->work_off[k] + (size_t)w0 * pl->slab[k], pl->slab[k]);
+  return rc != CMPC_OK ? rc : timing_end(pl, s, rec);
 }
 
 static int64_t heavy_first_batch(const cmpc_plan* pl) {
@@ -597,20 +591,13 @@ static int record_team_launch(cmpc_plan* pl, hipStream_t s, const cmpc::KParams&
   int rc = timing_begin(pl, 0, s, true, rec);
   if (rc != CMPC_OK) return rc;
   // one QP per CU: the one-workgroup-per-CU image (512 registers per lane, no spills)
-  if (team_one_per_cu(pl, B)) {
-    const unsigned g = (unsigned)(pl->team_grid1 < B ? pl->team_grid1 : B);
-    hipLaunchKernelGGL((cmpc::solve_team_kernel<kTeamWaves, 1>), dim3(g), dim3(64 * kTeamWaves), 0,
-                       s, kp, in, out, pl->d_lists, (int64_t)pl->p.max_batch, pl->d_counters,
-                       pl->d_counters + cmpc::kNumBins, pl->d_work, pl->team_slab);
-  } else {
-    const unsigned g = (unsigned)(pl->team_grid < B ? pl->team_grid : B);
-    hipLaunchKernelGGL((cmpc::solve_team_kernel<kTeamWaves, 2>), dim3(g), dim3(64 * kTeamWaves), 0,
-                       s, kp, in, out, pl->d_lists, (int64_t)pl->p.max_batch, pl->d_counters,
-                       pl->d_counters + cmpc::kNumBins, pl->d_work, pl->team_slab);
-  }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "solve_team_kernel launch");
-  return timing_end(pl, s, rec);
+  const bool one = team_one_per_cu(pl, B);
+  const TeamFn fn = one ? cmpc::solve_team_kernel<kTeamWaves, 1> : cmpc::solve_team_kernel<kTeamWaves, 2>;
+  const int grid = one ? pl->team_grid1 : pl->team_grid;
+  rc = launch(fn, "solve_team_kernel launch", (unsigned)(grid < B ? grid : B), 64 * kTeamWaves, 0, s,
+              kp, in, out, pl->d_lists, (int64_t)pl->p.max_batch, pl->d_counters,
+              pl->d_counters + cmpc::kNumBins, pl->d_work, pl->team_slab);
+  return rc != CMPC_OK ? rc : timing_end(pl, s, rec);
 }
 
 static int solve_impl(cmpc_plan* pl, int64_t B, const cmpc::Inputs& in, const cmpc::Outputs& out,
@@ -623,20 +610,18 @@ static int solve_impl(cmpc_plan* pl, int64_t B, const cmpc::Inputs& in, const cm
   // at most one wave per SIMD: latency-bound, the condensation with fewer MFMAs wins
   kp.latency_mode = (B <= 4LL * pl->cus) ? 1 : 0;
   if (B <= 1024) {  // one workgroup bins the batch and zeroes the queue heads (no memset)
-    hipLaunchKernelGGL(cmpc::bin_small_kernel, dim3(1), dim3(1024), 0, st, pl->kp.N, (int)B,
-                       in.contact, pl->d_counters, pl->d_counters + cmpc::kNumBins, pl->d_lists,
-                       pl->p.max_batch);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "bin_small_kernel launch");
+    rc = launch(cmpc::bin_small_kernel, "bin_small_kernel launch", 1, 1024, 0, st, pl->kp.N, (int)B,
+                in.contact, pl->d_counters, pl->d_counters + cmpc::kNumBins, pl->d_lists,
+                pl->p.max_batch);
+    if (rc != CMPC_OK) return rc;
   } else {
     e = hipMemsetAsync(pl->d_counters, 0, 2 * cmpc::kNumBins * sizeof(int), st);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
     const int threads = 256;
     const unsigned blocks = (unsigned)((B + threads - 1) / threads);
-    hipLaunchKernelGGL(cmpc::bin_kernel, dim3(blocks), dim3(threads), 0, st, pl->kp.N, B,
-                       in.contact, pl->d_counters, pl->d_lists, pl->p.max_batch);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "bin_kernel launch");
+    rc = launch(cmpc::bin_kernel, "bin_kernel launch", blocks, threads, 0, st, pl->kp.N, B,
+                in.contact, pl->d_counters, pl->d_lists, pl->p.max_batch);
+    if (rc != CMPC_OK) return rc;
   }
   // small batches: a team of kTeamWaves waves per QP, all bins in one kernel on the caller's
   // stream (measured faster than one wave per QP up to B = 4 x CUs on configs 1-3, slower from
@@ -704,29 +689,21 @@ static int solve_impl(cmpc_plan* pl, int64_t B, const cmpc::Inputs& in, const cm
 int cmpc_build_dynamics(cmpc_plan* pl, int64_t B, float dt, const float* mass,
                         const float* inertia, const float* r_feet, const float* xref, float* Ad,
                         float* Bd, float* gd, void* stream) {
-  if (!pl) return fail(CMPC_E_INVALID, "cmpc_build_dynamics: null plan");
-  if (int rc = check_device(pl, "cmpc_build_dynamics")) return rc;
-  if (B < 0) return fail(CMPC_E_INVALID, "cmpc_build_dynamics: negative batch");
+  if (int rc = check_pipeline(pl, "cmpc_build_dynamics", B < 0)) return rc;
   if (!(dt > 0.f) || !std::isfinite(dt)) return fail(CMPC_E_INVALID, "cmpc_build_dynamics: dt must be > 0");
   if (B == 0) return CMPC_OK;
   if (!mass || !inertia || !r_feet || !xref || !Ad || !Bd || !gd)
     return fail(CMPC_E_INVALID, "cmpc_build_dynamics: null array argument");
   // (grid-stride: ~32 resident waves per CU)
-  hipLaunchKernelGGL(cmpc::dynamics_kernel, dim3(grid_stride_blocks(B)), dim3(64), 0,
-                     (hipStream_t)stream, pl->kp.N, (double)dt, B, mass, inertia, r_feet, xref, Ad,
-                     Bd, gd);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "dynamics_kernel launch");
-  return CMPC_OK;
+  return launch(cmpc::dynamics_kernel, "dynamics_kernel launch", grid_stride_blocks(B), 64, 0, stream,
+                pl->kp.N, (double)dt, B, mass, inertia, r_feet, xref, Ad, Bd, gd);
 }
 
 int cmpc_generate_traj(cmpc_plan* pl, int64_t B, double dt, const float* x0, double* pos_des,
                        const float* cmd, const double* t_now, const double* gait,
                        const float* foot_lever, const float* hip, float* xref, uint8_t* contact,
                        float* r_feet, void* stream) {
-  if (!pl) return fail(CMPC_E_INVALID, "cmpc_generate_traj: null plan");
-  if (int rc = check_device(pl, "cmpc_generate_traj")) return rc;
-  if (B < 0) return fail(CMPC_E_INVALID, "cmpc_generate_traj: negative batch");
+  if (int rc = check_pipeline(pl, "cmpc_generate_traj", B < 0)) return rc;
   if (!(dt > 0.0) || !std::isfinite(dt)) return fail(CMPC_E_INVALID, "cmpc_generate_traj: dt must be > 0");
   if (B == 0) return CMPC_OK;
   if (!x0 || !pos_des || !cmd || !t_now || !gait || !foot_lever || !hip || !xref || !contact ||
@@ -734,12 +711,8 @@ int cmpc_generate_traj(cmpc_plan* pl, int64_t B, double dt, const float* x0, dou
     return fail(CMPC_E_INVALID, "cmpc_generate_traj: null array argument");
   // one wave per group of cmpc::kTrajGroup robots (grid-stride over groups)
   const unsigned blocks = grid_stride_blocks((B + cmpc::kTrajGroup - 1) / cmpc::kTrajGroup);
-  hipLaunchKernelGGL(cmpc::traj_group_kernel, dim3(blocks), dim3(64), 0,
-                     (hipStream_t)stream, pl->kp.N, dt, B, x0, pos_des, cmd, t_now, gait,
-                     foot_lever, hip, xref, contact, r_feet);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "traj_group_kernel launch");
-  return CMPC_OK;
+  return launch(cmpc::traj_group_kernel, "traj_group_kernel launch", blocks, 64, 0, stream, pl->kp.N,
+                dt, B, x0, pos_des, cmd, t_now, gait, foot_lever, hip, xref, contact, r_feet);
 }
 
 int cmpc_leg_torque(cmpc_plan* pl, int64_t B, const double* t, const double* gait,
@@ -748,9 +721,7 @@ int cmpc_leg_torque(cmpc_plan* pl, int64_t B, const double* t, const double* gai
                     const double* dq, const double* Jdot_dq, const double* foot_pos,
                     const double* foot_vel, const double* body, const double* hip,
                     double* state, double tau_max, double* tau, void* stream) {
-  if (!pl) return fail(CMPC_E_INVALID, "cmpc_leg_torque: null plan");
-  if (int rc = check_device(pl, "cmpc_leg_torque")) return rc;
-  if (B < 0) return fail(CMPC_E_INVALID, "cmpc_leg_torque: negative batch");
+  if (int rc = check_pipeline(pl, "cmpc_leg_torque", B < 0)) return rc;
   if (force_stride < 12) return fail(CMPC_E_INVALID, "cmpc_leg_torque: force_stride must be >= 12");
   if (!std::isfinite(tau_max)) return fail(CMPC_E_INVALID, "cmpc_leg_torque: tau_max must be finite");
   if (B == 0) return CMPC_OK;
@@ -760,32 +731,24 @@ int cmpc_leg_torque(cmpc_plan* pl, int64_t B, const double* t, const double* gai
   cmpc::LegArgs a{t, gait, force, force_stride, J_foot, J_full, M, C, g, dq, Jdot_dq, foot_pos,
                   foot_vel, body, hip, state, tau_max, tau};
   // (one wave per robot)
-  hipLaunchKernelGGL(cmpc::leg_kernel, dim3(grid_stride_blocks(B, 16384)), dim3(64), 0,
-                     (hipStream_t)stream, B, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "leg_kernel launch");
-  return CMPC_OK;
+  return launch(cmpc::leg_kernel, "leg_kernel launch", grid_stride_blocks(B, 16384), 64, 0, stream,
+                B, a);
 }
 
 int cmpc_srb_step(cmpc_plan* pl, int64_t B, int nsub, double dt, const double* t_now,
                   const double* gait, const float* mass, const float* inertia_body,
                   const float* force, int64_t force_stride, const float* hip, float* x,
                   float* feet, uint8_t* contact_state, void* stream) {
-  if (!pl) return fail(CMPC_E_INVALID, "cmpc_srb_step: null plan");
-  if (int rc = check_device(pl, "cmpc_srb_step")) return rc;
-  if (B < 0 || nsub < 0) return fail(CMPC_E_INVALID, "cmpc_srb_step: negative batch or nsub");
+  if (int rc = check_pipeline(pl, "cmpc_srb_step", B < 0 || nsub < 0, ": negative batch or nsub"))
+    return rc;
   if (!(dt > 0.0) || !std::isfinite(dt)) return fail(CMPC_E_INVALID, "cmpc_srb_step: dt must be > 0");
   if (force_stride < 12) return fail(CMPC_E_INVALID, "cmpc_srb_step: force_stride must be >= 12");
   if (B == 0 || nsub == 0) return CMPC_OK;
   if (!t_now || !gait || !mass || !inertia_body || !force || !hip || !x || !feet || !contact_state)
     return fail(CMPC_E_INVALID, "cmpc_srb_step: null array argument");
   const unsigned blocks = (unsigned)((B + 255) / 256);
-  hipLaunchKernelGGL(cmpc::srb_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, B, nsub,
-                     dt, t_now, gait, mass, inertia_body, force, force_stride, hip, x, feet,
-                     contact_state);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "srb_kernel launch");
-  return CMPC_OK;
+  return launch(cmpc::srb_kernel, "srb_kernel launch", blocks, 256, 0, stream, B, nsub, dt, t_now,
+                gait, mass, inertia_body, force, force_stride, hip, x, feet, contact_state);
 }
 
 int cmpc_plan_set_timing(cmpc_plan* pl, int enable) {

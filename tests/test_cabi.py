@@ -28,7 +28,17 @@ def test_exports_every_declared_symbol(lib):
     for s in syms:
         assert hasattr(lib, s), s
     from cmpc import _lib
-    assert set(_lib.EXPORTS) <= set(syms)
+    assert set(_lib.EXPORTS) == set(syms)
+
+
+def test_every_export_has_its_prototype(lib):
+    """_lib.load declares each entry of its table on the library it loads."""
+    from cmpc import _lib
+    for name in _lib.EXPORTS:
+        argtypes, restype = _lib.PROTOTYPES[name]
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and list(fn.argtypes) == list(argtypes), name
+        assert fn.restype is restype, name
 
 
 def test_defaults_are_reference_constants(lib):
@@ -84,6 +94,16 @@ def test_null_arguments(lib):
     assert "cmpc_build_dynamics" in lib.cmpc_last_error().decode()
     assert lib.cmpc_solve_warm(None, 1, *([None] * 13)) == -22
     assert "cmpc_solve_warm" in lib.cmpc_last_error().decode()
+    assert lib.cmpc_solve_ref(None, 1, *([None] * 13)) == -22
+    assert "cmpc_solve_ref" in lib.cmpc_last_error().decode()
+    from cmpc import _lib
+    assert lib.cmpc_solve_io_run(None, 1, None, None) == -22
+    assert "cmpc_solve_io_run" in lib.cmpc_last_error().decode()
+    short = _lib.CSolveIO()
+    short.size = _lib.CSolveIO.Ad.offset - 1
+    assert lib.cmpc_solve_io_run(None, 1, ctypes.byref(short), None) == -22
+    msg = lib.cmpc_last_error().decode()
+    assert "cmpc_solve_io_run" in msg and "size" in msg
     assert lib.cmpc_generate_traj(None, 1, 0.02, *([None] * 11)) == -22
     assert "cmpc_generate_traj" in lib.cmpc_last_error().decode()
     assert lib.cmpc_leg_torque(None, 1, None, None, None, 12, *([None] * 12), 45.0, None, None) == -22
