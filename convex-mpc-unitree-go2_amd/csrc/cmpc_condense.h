@@ -209,7 +209,8 @@ __device__ __forceinline__ void mirror_diagonals(Smem<NC>& s, f4 (&M)[Cfg<NC>::N
       if (16 * I >= n) continue;  // uniform
       f4 v = M[tile_index(I, I)];
       const int pc = 16 * I + c;
-      const int kc = (pc < n) ? s.par[pc] : N;
+      const int kp = s.par[pc];  // (pc < NC: read whatever n is, then selected -- no exec region)
+      const int kc = (pc < n) ? kp : N;
       const i4 kr4 = *reinterpret_cast<const i4*>(&s.par[16 * I + 4 * g]);
       const f4 tr = *reinterpret_cast<const f4*>(&T[256 * (I - I0) + c * 16 + 4 * g]);
 #pragma unroll
@@ -323,7 +324,7 @@ __device__ __forceinline__ void condense_tiles_bc(Smem<NC>& s, const KParams& P,
 // the lower part of a diagonal tile; the rest of a diagonal tile is mirrored, as in the
 // block-row form.  Every tile is then SIX MFMAs (two K = 12 products, 3 each) instead of the
 // three per active step of the forward form: ~240 MFMAs for n = 120 instead of 1,248 (936 in
-// the block-row form), with V = N b three MFMAs per 16-param chunk, parked in the G slab.  fp32
+// the block-row form), with V = N b three MFMAs per 16-param chunk, kept in registers.  fp32
 // error on the fixture matrices (unit-diagonal scaled, vs float64): 2.6e-7 against 4.1e-7 for
 // the step-by-step products.  The solve checks N^2 = 0 exactly per instance (nilpotent_step);
 // any other A takes the general forms above.
@@ -344,7 +345,21 @@ __device__ __forceinline__ void condense_tiles_nil(Smem<NC>& s, const KParams& P
   const int N = P.N;
   n = uniform(n);
   const int TA = (n + 15) >> 4;
-  float* Vs = s.G;  // V = N b, param-major [p][12] (the G slab is free while condensing)
+  float q2[3];
+#pragma unroll
+  for (int q = 0; q < 3; ++q) q2[q] = s.Q2[3 * g + q];
+  // The column operands (u, v) of every chunk, once: each is reused by every tile row below it
+  // (loaded per tile instead: 7 LDS reads between every tile's MFMAs; caching them took config 3
+  // 9.09 -> 8.60 ms, config 2 at 65,536 10.55 -> 9.99 ms, A/B in one GPU visit), and the
+  // chunk's step k: the tile row I = J below takes its sums over the steps from it, not from
+  // another LDS read per tile row.
+  // V = N b is three MFMAs per chunk, and lane (g, c) receives exactly the entries of V it uses as
+  // its own column operand (states 3g .. 3g + 2 of param 16 J + c): V stays in registers and never
+  // goes through the G slab.  The chunk's Bt column and step are read once, for V and for u, at
+  // p < NC whatever n is, and what lies past n is settled by selects: a read under `p < n` is an
+  // exec region of its own with its own wait, which was four serial LDS round trips per chunk.
+  float uc[C::TT][3], vc[C::TT][3];
+  int kc[C::TT];
   {
     // K = 12 state layout (as condense_tiles_fwd): accumulator position 4g + q holds state 3g + q
     const int sc = lane_state(c);
@@ -357,39 +372,28 @@ __device__ __forceinline__ void condense_tiles_nil(Smem<NC>& s, const KParams& P
     WSYNC();
 #pragma unroll
     for (int J = 0; J < C::TT; ++J) {
-      if (J >= TA) continue;  // uniform
-      const int p = 16 * J + c;
-      float bt[3];
+      if (J >= TA) {  // uniform: a padding chunk
+        kc[J] = 0;
 #pragma unroll
-      for (int q = 0; q < 3; ++q) bt[q] = (p < n) ? s.Bt[p * kBS + 3 * g + q] : 0.f;
+        for (int q = 0; q < 3; ++q) vc[J][q] = uc[J][q] = 0.f;
+        continue;
+      }
+      const int p = 16 * J + c;
+      const bool ok = p < n;
+      const int kp = s.par[p];
+      float bp[3];
+#pragma unroll
+      for (int q = 0; q < 3; ++q) bp[q] = s.Bt[p * kBS + 3 * g + q];
+      kc[J] = ok ? kp : 0;
+      const float kf = (float)kc[J];
       f4 d = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int q = 0; q < 3; ++q) d = mfma4(aN[q], bt[q], d);
+      for (int q = 0; q < 3; ++q) d = mfma4(aN[q], ok ? bp[q] : 0.f, d);
 #pragma unroll
-      for (int q = 0; q < 3; ++q) Vs[p * 12 + 3 * g + q] = d[q];
-    }
-  }
-  WSYNC();
-  float q2[3];
-#pragma unroll
-  for (int q = 0; q < 3; ++q) q2[q] = s.Q2[3 * g + q];
-  // the column operands (u, v) of every chunk, once: each is reused by every tile row below it
-  // (loaded per tile instead: 7 LDS reads between every tile's MFMAs; caching them took config 3
-  // 9.09 -> 8.60 ms, config 2 at 65,536 10.55 -> 9.99 ms, A/B in one gpurun call)
-  // (and the chunk's step k: the tile row I = J below takes its sums over the steps from it,
-  // not from another LDS read per tile row)
-  float uc[C::TT][3], vc[C::TT][3];
-  int kc[C::TT];
-#pragma unroll
-  for (int J = 0; J < C::TT; ++J) {
-    const int p = 16 * J + c;
-    const bool ok = J < TA && p < n;
-    kc[J] = ok ? s.par[p] : 0;
-    const float kf = (float)kc[J];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      vc[J][q] = ok ? Vs[p * 12 + 3 * g + q] : 0.f;
-      uc[J][q] = ok ? fmaf(-kf, vc[J][q], s.Bt[p * kBS + 3 * g + q]) : 0.f;
+      for (int q = 0; q < 3; ++q) {
+        vc[J][q] = ok ? d[q] : 0.f;
+        uc[J][q] = ok ? fmaf(-kf, vc[J][q], bp[q]) : 0.f;
+      }
     }
   }
 #pragma unroll

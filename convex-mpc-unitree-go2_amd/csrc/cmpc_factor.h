@@ -185,6 +185,17 @@ __device__ __forceinline__ void sweep_block_plain(SM& s, f4 (&M)[Cfg<NC>::NTL], 
   }
 }
 
+// The scaling and un-scaling passes of ldl_tiles form m[q] *= r[q] * cj on register pairs (q = 0, 1
+// and q = 2, 3): v_pk_mul_f32 rounds each half as the scalar multiply does, and the two passes are
+// 8 NTL multiplies per lane otherwise.  Not in the NC 192 kernel, which the pairs' temporaries
+// took from 0 to 40 spilled registers.
+template <int NC>
+constexpr bool kPackedScale = NC <= 160;
+__device__ __forceinline__ void scale_tile(f4& m, f2 t01, f2 t23) {
+  const f2 m01 = f2{m[0], m[1]} * t01, m23 = f2{m[2], m[3]} * t23;
+  m = f4{m01[0], m01[1], m23[0], m23[1]};
+}
+
 // ------------------------------------------------------------------------------------------
 // block LDL' factorization by the sweep operator (4 pivots per step, MFMA rank-4 updates)
 // ------------------------------------------------------------------------------------------
@@ -219,8 +230,12 @@ __device__ __forceinline__ void ldl_tiles(SM& s, f4 (&M)[Cfg<NC>::NTL], int n) {
     for (int J = 0; J <= I; ++J) {
       const float cj = s.ds[16 * J + c];
       f4& m = M[tile_index(I, J)];
+      if constexpr (kPackedScale<NC>) {
+        scale_tile(m, f2{ri[0], ri[1]} * f2{cj, cj}, f2{ri[2], ri[3]} * f2{cj, cj});
+      } else {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) m[q] *= ri[q] * cj;
+        for (int q = 0; q < 4; ++q) m[q] *= ri[q] * cj;
+      }
     }
   }
   const int ng = (n + 3) >> 2;
@@ -260,8 +275,14 @@ __device__ __forceinline__ void ldl_tiles(SM& s, f4 (&M)[Cfg<NC>::NTL], int n) {
     for (int J = 0; J <= I; ++J) {
       const float cj = s.ds[16 * J + c_r];
       f4& m = M[tile_index(I, J)];
+      if constexpr (!kPackedScale<NC>) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) m[q] *= (J < I) ? rinv[q] * cj : -(ri[q] * cj);
+        for (int q = 0; q < 4; ++q) m[q] *= (J < I) ? rinv[q] * cj : -(ri[q] * cj);
+      } else if (J < I) {  // compile-time after unrolling
+        scale_tile(m, f2{rinv[0], rinv[1]} * f2{cj, cj}, f2{rinv[2], rinv[3]} * f2{cj, cj});
+      } else {
+        scale_tile(m, -(f2{ri[0], ri[1]} * f2{cj, cj}), -(f2{ri[2], ri[3]} * f2{cj, cj}));
+      }
     }
   }
 }

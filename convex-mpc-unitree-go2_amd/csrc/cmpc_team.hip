@@ -261,13 +261,16 @@ __device__ __forceinline__ void team_factor(Smem<NC>& s, TeamSmem<NC, W>& ts, co
       for (int J = 0; J < TT; ++J) {
         if (J % W != w) continue;  // uniform
         if (16 * J >= n) continue;  // uniform
+        // (p < NC: Bt, par and the V slab are read whatever n is and what lies past n is settled
+        // by selects, here and below -- a read under `p < n` is an exec region with its own wait,
+        // as in condense_tiles_nil)
         const int p = 16 * J + c;
         float bt[3];
 #pragma unroll
-        for (int q = 0; q < 3; ++q) bt[q] = (p < n) ? s.Bt[p * kBS + 3 * g + q] : 0.f;
+        for (int q = 0; q < 3; ++q) bt[q] = s.Bt[p * kBS + 3 * g + q];
         f4 d = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int q = 0; q < 3; ++q) d = mfma4(aN[q], bt[q], d);
+        for (int q = 0; q < 3; ++q) d = mfma4(aN[q], (p < n) ? bt[q] : 0.f, d);
 #pragma unroll
         for (int q = 0; q < 3; ++q) Cs[p * 12 + 3 * g + q] = d[q];
       }
@@ -288,11 +291,13 @@ __device__ __forceinline__ void team_factor(Smem<NC>& s, TeamSmem<NC, W>& ts, co
       for (int h = 0; h < 2; ++h) {
         const int p = 16 * (h ? TT - 1 - pr : pr) + c;
         const bool ok = p < n;
-        const float kf = ok ? (float)s.par[p] : 0.f;
+        const int kp = s.par[p];
+        const float kf = ok ? (float)kp : 0.f;
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-          vc[h][q] = ok ? Cs[p * 12 + 3 * g + q] : 0.f;
-          uc[h][q] = ok ? fmaf(-kf, vc[h][q], s.Bt[p * kBS + 3 * g + q]) : 0.f;
+          const float vp = Cs[p * 12 + 3 * g + q], bp = s.Bt[p * kBS + 3 * g + q];
+          vc[h][q] = ok ? vp : 0.f;
+          uc[h][q] = ok ? fmaf(-kf, vc[h][q], bp) : 0.f;
         }
       }
 #pragma unroll
@@ -304,14 +309,16 @@ __device__ __forceinline__ void team_factor(Smem<NC>& s, TeamSmem<NC, W>& ts, co
         {
           const int p = 16 * I + c;
           const bool ok = p < n;
-          const int k = ok ? s.par[p] : 0;
+          const int kp = s.par[p];
+          const int k = ok ? kp : 0;
           const float kf = (float)k;
           float S0, S1, S2;
           step_sums(k, N, S0, S1, S2);
 #pragma unroll
           for (int q = 0; q < 3; ++q) {
-            const float vv = ok ? Cs[p * 12 + 3 * g + q] : 0.f;
-            const float uu = ok ? fmaf(-kf, vv, s.Bt[p * kBS + 3 * g + q]) : 0.f;
+            const float vp = Cs[p * 12 + 3 * g + q], bp = s.Bt[p * kBS + 3 * g + q];
+            const float vv = ok ? vp : 0.f;
+            const float uu = ok ? fmaf(-kf, vv, bp) : 0.f;
             x[q] = qd[q] * fmaf(S0, uu, S1 * vv);
             y[q] = qd[q] * fmaf(S1, uu, S2 * vv);
           }

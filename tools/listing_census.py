@@ -30,6 +30,12 @@ FUNCS = {
     "sweep_block_plain": ("cmpc_factor.h", "ldl_tiles + sweep"),
     "pivot_block": ("cmpc_factor.h", "ldl_tiles + sweep"),
     "panel_row": ("cmpc_factor.h", "ldl_tiles + sweep"),
+    "scale_tile": ("cmpc_factor.h", "ldl_tiles + sweep"),
+    "diag_element": ("cmpc_factor.h", "ldl_tiles + sweep"),
+    "condense_tiles_nil": ("cmpc_condense.h", "condense_tiles_nil"),
+    "step_sums": ("cmpc_condense.h", "condense_tiles_nil"),
+    "mirror_diagonals": ("cmpc_condense.h", "mirror_diagonals"),
+    "condense_finish": ("cmpc_condense.h", "condense_finish"),
     "polish_check": ("cmpc_polish.h", "polish_check"),
     "polish_setup": ("cmpc_polish.h", "polish_setup"),
     "stage_instance": ("cmpc_solve.h", "stage_instance"),
