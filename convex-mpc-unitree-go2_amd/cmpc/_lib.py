@@ -78,6 +78,14 @@ class CVjpIO(ctypes.Structure):
                           "g_R", "g_mu", "g_fz_min", "g_Ad", "g_Bd")
 
 
+class CJvpIO(ctypes.Structure):
+    """cmpc_jvp_io (include/cmpc.h): a batch whose forward-mode derivative is wanted, given the
+    tangents of its inputs, with the per-instance values of CSolveIO.  ``size`` is this mirror's
+    sizeof."""
+    _fields_ = _io_fields("Q", "R", "w", "faces", "face_tol", "d_x0", "d_xref", "d_gd", "d_Q",
+                          "d_R", "d_mu", "d_fz_min", "d_Ad", "d_Bd", "dw")
+
+
 class CRefineIO(ctypes.Structure):
     """cmpc_refine_io (include/cmpc.h): a batch of answers to refine and certify in float64, with
     the per-instance values of CSolveIO.  ``size`` is this mirror's sizeof."""
@@ -94,6 +102,8 @@ FACE_FZ_MIN, FACE_FX_POS, FACE_FX_NEG, FACE_FY_POS, FACE_FY_NEG = 1, 2, 4, 8, 16
 GAIN_OUTPUTS = ("K", "Vx", "Vxx", "u_star", "faces")
 # Plan.vjp's results: the input each gradient belongs to (field g_<name> of cmpc_vjp_io)
 VJP_OUTPUTS = ("x0", "xref", "gd", "Q", "R", "mu", "fz_min", "Ad", "Bd")
+# Plan.jvp's tangents: the input each belongs to (field d_<name> of cmpc_jvp_io)
+JVP_TANGENTS = VJP_OUTPUTS
 
 KKT_COLUMNS = ("cost", "stat", "prim", "comp")  # CMPC_KKT_COST .. CMPC_KKT_COMP
 
@@ -136,7 +146,7 @@ def _prototypes() -> dict:
     # the struct entries: (plan, B, const io*, stream)
     for name, io in (("cmpc_solve_io_run", CSolveIO), ("cmpc_kkt_run", CKktIO),
                      ("cmpc_gain_run", CGainIO), ("cmpc_vjp_run", CVjpIO),
-                     ("cmpc_refine_run", CRefineIO)):
+                     ("cmpc_refine_run", CRefineIO), ("cmpc_jvp_run", CJvpIO)):
         table[name] = ([vp, i64, ptr(io), vp], rc)
     return table
 

@@ -2,14 +2,18 @@
 
 ``solve(plan, ...)`` is :meth:`cmpc.Plan.solve` whose ``w`` carries a gradient: the backward
 pass is one :meth:`cmpc.Plan.vjp` launch (cmpc_vjp_run, include/cmpc.h) for the inputs that
-require one.
+require one, and forward-mode AD (``torch.autograd.forward_ad``) is one :meth:`cmpc.Plan.jvp`
+launch (cmpc_jvp_run) for the inputs that carry a tangent.  The ``torch.func`` transforms hand a
+``Function`` wrapped tensors without storage, which a native launch cannot take: ``jvp(plan, ...,
+tangents)`` below is the functional form for them.
 
 The gradient is that of the fp64 optimum on the faces of the friction pyramid the returned
 ``w`` holds, with that face set fixed -- the function :meth:`cmpc.Plan.gain` solves -- not of the
 fp32 ``w`` itself: the two differ by the solver's tolerance, and where ``w`` sits within
 ``face_tol`` of a face it does not hold at the true optimum (or the other way round) the
 gradient is that of the neighbouring piece of the piecewise-affine law.  It does
-not see a change of the face set, and it is first order only: a second backward raises.
+not see a change of the face set, and it is first order only: a second backward raises, and the
+tangent of forward mode carries no derivative of its own.
 """
 from __future__ import annotations
 
@@ -26,7 +30,9 @@ class _Solve(torch.autograd.Function):
         w, status, iters = plan.solve(Ad, Bd, gd, x0, xref, contact, mu=mu, fz_min=fz_min, Q=Q, R=R)
         ctx.plan, ctx.face_tol = plan, face_tol
         ctx.save_for_backward(Ad, Bd, gd, x0, xref, contact, mu, fz_min, Q, R, w, status)
+        ctx.save_for_forward(Ad, Bd, gd, x0, xref, contact, mu, fz_min, Q, R, w, status)
         ctx.mark_non_differentiable(status, iters)
+        ctx.set_materialize_grads(False)    # jvp: an input without a tangent arrives as None
         return w, status, iters
 
     @staticmethod
@@ -37,7 +43,7 @@ class _Solve(torch.autograd.Function):
         inputs = (Ad, Bd, gd, x0, xref, contact, mu, fz_min, Q, R)
         want = [n for n, need in zip(names, ctx.needs_input_grad[2:]) if n is not None and need]
         grads = [None] * 12
-        if not want:
+        if not want or gw is None:
             return tuple(grads)
         # (Plan.vjp launches on torch's current stream)
         res = ctx.plan.vjp(Ad, Bd, gd, x0, xref, contact,
@@ -51,6 +57,20 @@ class _Solve(torch.autograd.Function):
                 grads[2 + pos] = g
         return tuple(grads)
 
+    @staticmethod
+    def jvp(ctx, _plan, _tol, *tangents):
+        Ad, Bd, gd, x0, xref, contact, mu, fz_min, Q, R, w, status = ctx.saved_tensors
+        names = _PROBLEM + (None,) + _INSTANCE
+        given = {n: t.detach().to(torch.float32).contiguous()
+                 for n, t in zip(names, tangents) if n is not None and t is not None}
+        if not given:
+            return None, None, None
+        # (Plan.jvp launches on torch's current stream)
+        dw = ctx.plan.jvp(Ad, Bd, gd, x0, xref, contact, given, w=w, mu=mu, fz_min=fz_min, Q=Q,
+                          R=R, face_tol=ctx.face_tol).to(w.dtype)
+        dw[status == -10] = 0                            # an invalid instance: no tangent
+        return dw, None, None
+
 
 def solve(plan, Ad, Bd, gd, x0, xref, contact, mu=None, fz_min=None, Q=None, R=None,
           face_tol=None):
@@ -60,6 +80,23 @@ def solve(plan, Ad, Bd, gd, x0, xref, contact, mu=None, fz_min=None, Q=None, R=N
     gradient).  The backward pass calls :meth:`cmpc.Plan.vjp` with the saved inputs and ``w``
     for exactly the inputs that need a gradient, on the current stream, casts the float64
     results to each input's dtype, and gives a zero gradient to the rows of instances whose
-    status is -10 (an invalid entry).  See the module's note on which function the gradient
-    belongs to."""
+    status is -10 (an invalid entry).  Under forward-mode AD (``torch.autograd.forward_ad``)
+    the tangent of ``w`` is one :meth:`cmpc.Plan.jvp` launch for exactly the
+    inputs that carry a tangent, cast to ``w``'s dtype, zero in the rows of status -10.  See the
+    module's note on which function the derivative belongs to."""
     return _Solve.apply(plan, face_tol, Ad, Bd, gd, x0, xref, contact, mu, fz_min, Q, R)
+
+
+def jvp(plan, Ad, Bd, gd, x0, xref, contact, tangents, mu=None, fz_min=None, Q=None, R=None,
+        face_tol=None):
+    """The functional form of forward mode: :meth:`cmpc.Plan.solve` and then one
+    :meth:`cmpc.Plan.jvp` launch on the faces its ``w`` holds -> ``(w, status, iters, dw)``.
+    ``tangents`` is a non-empty dict from input name to a tensor of that input's shape (cast to
+    fp32); ``dw`` has ``w``'s dtype and is zero in the rows of status -10, as the tangent
+    ``solve`` carries under ``torch.autograd.forward_ad``."""
+    w, status, iters = plan.solve(Ad, Bd, gd, x0, xref, contact, mu=mu, fz_min=fz_min, Q=Q, R=R)
+    given = {n: t.detach().to(torch.float32).contiguous() for n, t in tangents.items()}
+    dw = plan.jvp(Ad, Bd, gd, x0, xref, contact, given, w=w, mu=mu, fz_min=fz_min, Q=Q, R=R,
+                  face_tol=face_tol).to(w.dtype)
+    dw[status == -10] = 0
+    return w, status, iters, dw

@@ -503,6 +503,51 @@ class Plan:
         self._run_io("cmpc_vjp_run", io, B, stream)
         return res
 
+    def jvp(self, Ad, Bd, gd, x0, xref, contact, tangents, w=None, faces=None, mu=None,
+            fz_min=None, Q=None, R=None, face_tol=None, out=None, stream=None):
+        """Forward-mode derivative of B solved instances on the device (cmpc_jvp_run,
+        include/cmpc.h): how the whole answer moves with the inputs.
+
+        ``Ad`` .. ``contact``, ``mu`` / ``fz_min`` / ``Q`` / ``R``, ``w`` / ``faces`` and
+        ``face_tol`` as for :meth:`gain`.  ``tangents`` is a non-empty dict from input name, one of
+        ``("x0", "xref", "gd", "Q", "R", "mu", "fz_min", "Ad", "Bd")``, to an fp32 device tensor
+        of that input's shape (``Q`` / ``R`` (B, 12) and ``mu`` / ``fz_min`` (B,) whether the
+        values come from the plan or from a row); an input that is not named does not move, and
+        work that only absent tangents need is skipped.  Returns ``dw`` (B, 24N) float64 in w's
+        layout, states then forces: the directional derivative of the fp64 optimum on the held
+        faces, the face set fixed (:meth:`gain`'s ``u_star`` and its rollout) -- :meth:`vjp`'s
+        Jacobian applied from the other side.  An instance with an inconsistent mask or an
+        invalid mu / fz_min entry or Q / R row gets a row of NaN.  ``out`` is a preallocated
+        ``dw``.  Asynchronous on ``stream`` (default: torch's current stream), no allocation
+        when ``out`` is given, graph-capturable; the inputs are not modified and B is not
+        limited by max_batch."""
+        self._need("cmpc_jvp_run", "jvp")
+        tangents = dict(tangents)
+        unknown = [n for n in tangents if n not in _lib.JVP_TANGENTS]
+        if unknown or not tangents:
+            raise ValueError(f"jvp: tangents {tuple(tangents)} must name a non-empty subset of "
+                             f"{_lib.JVP_TANGENTS}")
+        if w is None and faces is None:
+            raise ValueError("jvp needs w or faces: one must name the held faces")
+        N = self.params.N
+        B = Ad.shape[0]
+        if B < 1:
+            raise ValueError("jvp needs at least one instance")
+        io = _lib.CJvpIO()
+        io.size = ctypes.sizeof(_lib.CJvpIO)
+        self._fill_io(io, _eval_spec(B, N), _problem(Ad, Bd, gd, x0, xref, contact),
+                      dict(w=w, faces=faces, mu=mu, fz_min=fz_min, Q=Q, R=R))
+        shapes = dict(x0=(B, 12), xref=(B, N, 12), gd=(B, 12), Q=(B, 12), R=(B, 12), mu=(B,),
+                      fz_min=(B,), Ad=(B, 12, 12), Bd=(B, N, 12, 12))
+        self._fill_io(io, {"d_" + n: (torch.float32, s) for n, s in shapes.items()},
+                      {"d_" + n: t for n, t in tangents.items()}, {})
+        if out is None:
+            out = torch.empty((B, 24 * N), dtype=torch.float64, device=self.device)
+        io.dw = self._address(out, "out", torch.float64, (B, 24 * N))
+        io.face_tol = 0.0 if face_tol is None else float(face_tol)
+        self._run_io("cmpc_jvp_run", io, B, stream)
+        return out
+
     def refine(self, Ad, Bd, gd, x0, xref, contact, w=None, faces=None, mu=None, fz_min=None,
                Q=None, R=None, face_tol=0.0, max_rounds=8, prim_tol=0.0, dual_tol=0.0, w_out=None,
                status=None, want=("info", "res"), out=None, stream=None):

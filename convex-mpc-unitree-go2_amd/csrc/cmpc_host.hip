@@ -23,6 +23,7 @@
 #include "cmpc_gain.hip"      // feedback gain and value function on the held faces
 #include "cmpc_vjp.hip"       // gradients of a loss through the optimum on the held faces
 #include "cmpc_refine.hip"    // certified float64 refinement around the optimum on the held faces
+#include "cmpc_jvp.hip"       // forward-mode derivatives of the optimum on the held faces
 
 constexpr int kNumGroups = 3;  // solve kernels (register classes), see solve_group_kernel
 static_assert(kNumGroups == CMPC_NUM_SOLVE_KERNELS, "one timing slot per solve kernel");
@@ -137,7 +138,7 @@ int io_copy(const IO* io, size_t min_size, const char* what, const char* type, I
   return CMPC_OK;
 }
 
-// The checks of an evaluation entry (cmpc_kkt_io, cmpc_gain_io, cmpc_vjp_io, cmpc_refine_io) after io_copy: plan, B, the six
+// The checks of an evaluation entry (cmpc_kkt_io, cmpc_gain_io, cmpc_vjp_io, cmpc_refine_io, cmpc_jvp_io) after io_copy: plan, B, the six
 // problem arrays, face_tol, the device.  `own`: the entry's own required arrays are there;
 // `between`: the message of a failed check of the entry's own that ranks after the arrays, or NULL.
 template <class IO>
@@ -172,7 +173,8 @@ cmpc::ProblemArgs problem_args(const cmpc_plan* pl, const IO& a) {
   return k;
 }
 
-// the held-face part of the argument blocks of cmpc_gain_run, cmpc_vjp_run and cmpc_refine_run:
+// the held-face part of the argument blocks of cmpc_gain_run, cmpc_vjp_run, cmpc_refine_run and
+// cmpc_jvp_run:
 // given faces take the place of w's unless the kernel reads w for more than its faces (keep_w)
 template <class IO>
 cmpc::HeldArgs held_args(const cmpc_plan* pl, const IO& a, bool keep_w) {
@@ -489,6 +491,23 @@ int cmpc_vjp_run(cmpc_plan* pl, int64_t B, const cmpc_vjp_io* io, void* stream) 
                         a.g_mu, a.g_fz_min, a.g_Ad, a.g_Bd};
   const size_t dyn = (size_t)k.p.N * cmpc::kVjpSlot * sizeof(double);
   return launch_eval(cmpc::vjp_kernel, "vjp_kernel launch", B, dyn, stream, k, B);
+}
+
+int cmpc_jvp_run(cmpc_plan* pl, int64_t B, const cmpc_jvp_io* io, void* stream) {
+  cmpc_jvp_io a;
+  if (int rc = io_copy(io, offsetof(cmpc_jvp_io, dw) + sizeof(io->dw), "cmpc_jvp_run",
+                       "cmpc_jvp_io", a))
+    return rc;
+  const bool any = a.d_x0 || a.d_xref || a.d_gd || a.d_Q || a.d_R || a.d_mu || a.d_fz_min ||
+                   a.d_Ad || a.d_Bd;
+  if (int rc = check_problem(pl, B, a, a.dw, "cmpc_jvp_run",
+                             !(a.w || a.faces) ? kNoFaces
+                             : !any ? ": every tangent is null (one must be given)" : nullptr))
+    return rc;
+  const cmpc::JvpArgs k{held_args(pl, a, false), a.d_x0, a.d_xref, a.d_gd, a.d_Q, a.d_R,
+                        a.d_mu, a.d_fz_min, a.d_Ad, a.d_Bd, a.dw};
+  const size_t dyn = (size_t)k.p.N * cmpc::kGainSlot * sizeof(double);  // every step's (K_k, kappa_k)
+  return launch_eval(cmpc::jvp_kernel, "jvp_kernel launch", B, dyn, stream, k, B);
 }
 
 int cmpc_refine_run(cmpc_plan* pl, int64_t B, const cmpc_refine_io* io, void* stream) {

@@ -1,8 +1,8 @@
 // cmpc_lq.h -- the equality-constrained LQ problem on the faces a solved instance holds, which
-// cmpc_gain.hip, cmpc_vjp.hip and cmpc_refine.hip all evaluate: the held-face part
-// of their argument blocks and its two loads, the lane's mask and its affine set, the affine
+// cmpc_gain.hip, cmpc_vjp.hip, cmpc_refine.hip and cmpc_jvp.hip all evaluate: the
+// held-face part of their argument blocks and its two loads, the lane's mask and its affine set, the affine
 // terms d_k, the backward Riccati recursion on the f64 matrix cores and the forward pass that
-// keeps whole trajectories.  Included by those three files only, on top of cmpc_problem.h.  The
+// keeps whole trajectories.  Included by those four files only, on top of cmpc_problem.h.  The
 // masks one entry writes are the masks another reads and refine's point is gain's u_star, so
 // each of these exists once.
 //
@@ -129,6 +129,7 @@ struct GainLds {
   double *GM, *Y;       // [12 * (24 + NAFF)] [G | rhs], 16-byte aligned; [12 * (12 + NAFF)] [Kp | kp ..]
   double* K;            // keep_steps ? N : 1 slots of (K_k [12][12], kappa_k [12], .. NAFF of them)
   const float* Gw;      // NAFF == 2: gw [24N], states then forces
+  const double *Ts, *Tr, *Te;  // TAN: per step, the state term, the force term r and the offset e_k
 };
 
 // A pointer into LDS that says so in its type: what gain_recursion<2> reads the bundle through.
@@ -179,10 +180,18 @@ __device__ inline void gain_affine(const ProblemLds& sp, const GainLds& s, int N
 // in the slots of s.K, P_0 (not mirrored) in s.P and q_0 (q'_0) in qreg on the lanes with
 // (lane & 15) == 12 (13), entry (lane >> 4) + 4 r in qreg[r].  The caller's barrier stands before
 // the call; the last step's barrier ends it.
-template <int NAFF>
+//
+// TAN (cmpc_jvp.hip, NAFF == 1): column 12 carries a tangent problem instead of the instance's
+// own, the same matrices with the general linear terms of s.Ts, s.Tr, s.Te:
+//   s = q_{k+1} + Ts_k    a force term r = Tr_k (Z'r joins the solve's right-hand side, K_k'r
+//   joins q_k, as the adjoint's)    x_{k+1} = Ad x_k + Bd_k u_k + Te_k
+// and the caller fills s.Cv with the tangent's c_k and s.Dv with Bd_k c_k + Te_k.  Its c_k need
+// not satisfy Z'R c = 0: the caller adds R c_k to Tr_k.
+template <int NAFF, bool TAN = false>
 __device__ __forceinline__ void gain_recursion(ProblemLds& sp, const GainLds& s, int N,
                                                int keep_steps, int lane, double qreg[3]) {
   static_assert(NAFF == 1 || NAFF == 2, "one affine column, or the adjoint's next to it");
+  static_assert(!TAN || NAFF == 1, "the tangent's terms take the place of column 12");
   constexpr int GW = 24 + NAFF, YW = 12 + NAFF;  // row strides of [G | rhs] and [Kp | kp ..]
   auto& [sBd, sAd, sXr, sGX, sQ, sR, sC] = sp;
   using PF = std::conditional_t<NAFF == 2, lds_ptr<const float>, const float*>;
@@ -233,6 +242,9 @@ __device__ __forceinline__ void gain_recursion(ProblemLds& sp, const GainLds& s,
         sreg[q_] = c == 13 ? fma(0.5, (double)sGw[k * 12 + rq], qreg[q_])
                            : qreg[q_] - sQ[rq] * (double)sXr[k * 12 + rq];
         rb[q_] = c == 13 ? 0.5 * (double)sGwU[k * 12 + rq] : 0.0;
+      } else if constexpr (TAN) {
+        sreg[q_] = qreg[q_] + s.Ts[k * 12 + rq];
+        rb[q_] = c == 12 ? s.Tr[k * 12 + rq] : 0.0;
       } else {
         sreg[q_] = qreg[q_] - sQ[rq] * (double)sXr[k * 12 + rq];
       }
@@ -264,6 +276,15 @@ __device__ __forceinline__ void gain_recursion(ProblemLds& sp, const GainLds& s,
                                             fma((double)sZy[k * 4 + leg], (double)ru[1], (double)ru[2]))
                                       : (double)ru[ax];
             m = fma(0.5, zr, m);
+          }
+        }
+        if constexpr (TAN) {  // column 12 of M takes Z'r on the slots in use
+          if (c == 12 && Dk[i] != 0.0) {
+            const int leg = i / 3, ax = i - 3 * leg;
+            const double* const ru = s.Tr + k * 12 + 3 * leg;
+            m += ax == 2 ? fma((double)sZx[k * 4 + leg], ru[0],
+                               fma((double)sZy[k * 4 + leg], ru[1], ru[2]))
+                         : ru[ax];
           }
         }
         sGM[i * GW + 12 + c] = m;
@@ -317,11 +338,14 @@ __device__ __forceinline__ void gain_recursion(ProblemLds& sp, const GainLds& s,
       kb[q_] = c < YW ? v : 0.0;
       kpb[q_] = c < YW ? yv : 0.0;
       ka[q_] = c < 12 ? yv * Dk[rq] : 0.0;
-      if constexpr (NAFF == 2) kt[q_] = c < 12 ? v : 0.0;  // A operand K_k'
+      if constexpr (NAFF == 2 || TAN) kt[q_] = c < 12 ? v : 0.0;  // A operand K_k'
       if (c < 12) Kk[rq * 12 + c] = v;
       else if (c < YW) Kk[12 * c + rq] = v;  // kappa_k at 144, kappa'_k at 156
     }
-    const gain_d4 ad0 = {adg[0], adg[1], adg[2], 0.0};
+    gain_d4 ad0 = {adg[0], adg[1], adg[2], 0.0};
+    if constexpr (TAN) {  // e_k in gd's place
+      if (c == 12) ad0 = {s.Te[k * 12 + g], s.Te[k * 12 + 4 + g], s.Te[k * 12 + 8 + g], 0.0};
+    }
     // [A_cl | d_cl | d'_cl] = [Ad | gd | 0] + Bd_k [K_k | kappa_k | kappa'_k]
     gain_d4 AC = gain_mm(ab, kb, ad0);
     double acb[3], sacb[3];
@@ -332,7 +356,7 @@ __device__ __forceinline__ void gain_recursion(ProblemLds& sp, const GainLds& s,
     for (int r_ = 0; r_ < 3; ++r_) sacb[r_] = aff ? SAC[r_] + sreg[r_] : SAC[r_];
     gain_d4 Pn = gain_mm(acb, sacb, zero);  // [A_cl'S A_cl | A_cl'(S d_cl + s) | A_cl'(S d'_cl + s')]
     Pn = gain_mm(ka, kpb, Pn);              // + [Kp'D Kp | Kp'D kp | Kp'D kp']
-    if constexpr (NAFF == 2) Pn = gain_mm(kt, rb, Pn);  // + [0 | 0 | K_k'r]
+    if constexpr (NAFF == 2 || TAN) Pn = gain_mm(kt, rb, Pn);  // + [0 | 0 | K_k'r] (TAN: column 12)
 #pragma unroll
     for (int r_ = 0; r_ < 3; ++r_) {
       if (c < 12) sP[(g + 4 * r_) * 12 + c] = Pn[r_];

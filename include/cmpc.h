@@ -395,6 +395,65 @@ typedef struct cmpc_vjp_io {
 } cmpc_vjp_io;
 int cmpc_vjp_run(cmpc_plan* plan, int64_t B, const cmpc_vjp_io* io, void* stream);
 
+/* Forward-mode derivatives of B solved instances, on the device: how the whole answer moves when
+ * the inputs change.  The function differentiated is cmpc_vjp_io's: w*(theta) = (x_1..x_N,
+ * u_0..u_{N-1}), the minimiser of 1/2 w'Hw + g'w over the dynamics and the held faces, the face
+ * set fixed.  With the restricted QP written [[H, E'], [E, 0]] [w; nu] = [-g; b] as there (the
+ * same rows, the same sign of nu), a change d_theta of the inputs moves the solution by
+ *   [[H, E'], [E, 0]] [dw; dnu] = [-(dH w + dg + dE' nu);  db - dE w]
+ * which is the same LQ problem with other linear terms:
+ *   d_x0     [B][12]          dx_0 = d_x0
+ *   d_gd     [B][12]          the offset e_k = d_gd + d_Ad x_k + d_Bd_k u_k of every dynamics row
+ *   d_Ad     [B][12][12]      e_k, and -d_Ad' nu_{k+1} on dx_{k+1} (nu_N = 0)
+ *   d_Bd     [B][N][12][12]   e_k, and -d_Bd_k' nu_k on du_k
+ *   d_xref   [B][N][12]       -2Q o d_xref_k on dx_{k+1}
+ *   d_Q      [B][12]          2 d_Q o (x_{k+1} - xref_k) on dx_{k+1}
+ *   d_R      [B][12]          2 d_R o u_k on du_k
+ *   d_mu     [B]              a held friction row fx - s mu fz = 0 (s = +-1) moves to
+ *                             dfx - s mu dfz = s d_mu fz, and its multiplier puts
+ *                             -s d_mu nu_r on the leg's dfz; the same for fy
+ *   d_fz_min [B]              a held fz = fz_min row moves to dfz = d_fz_min
+ * All fp32 of the inputs' shapes, widened exactly, all nullable, at least one required (else
+ * CMPC_E_INVALID).  A NULL tangent and an array of zeros give equal results (the sign of a zero
+ * may differ); work that only absent tangents need (the costate pass for d_Ad, d_Bd, d_mu; the
+ * primal solution where only d_x0, d_xref, d_gd, d_fz_min are given) is skipped.  d_Q, d_R, d_mu
+ * and d_fz_min apply to the instance's values whether they came from the plan or from a row.  A
+ * swing leg keeps df = 0, and a leg that holds both signs of an axis stays pinned at 0 whatever
+ * d_mu and d_fz_min are (cmpc_gain_io's mask rule): their entries of dw are exactly 0.
+ *   Ad..contact, mu, fz_min, Q, R, w, faces, face_tol   as in cmpc_gain_io; w and faces both
+ *                             NULL: CMPC_E_INVALID
+ *   dw       [B][24N]  fp64   required; dx_1..dx_N, then du_0..du_{N-1}
+ * The tangent is that of the fp64 optimum on the faces named, not of the fp32 w_out, and it does
+ * not see a change of the face set.  An instance with an inconsistent mask, or with a mu / fz_min
+ * entry or Q / R row that is invalid by the rules of cmpc_solve_io, gets NaN in its whole row of
+ * dw; it never fails the call and the other instances are unaffected.
+ * `size` is the caller's sizeof of the struct (fields past it read as NULL or 0); it must reach
+ * past `dw`.  B >= 1; no workspace is used, so the plan's max_batch does not limit B.  Each sum
+ * runs in a fixed order: the results are bitwise repeatable and do not depend on B or on the
+ * instance's place in the batch.  Same guarantees as cmpc_solve: asynchronous on `stream`, no
+ * allocation, no host synchronisation, graph-capturable; the plan's device must be current. */
+typedef struct cmpc_jvp_io {
+  uint32_t size;            /* sizeof of this struct in the caller's header */
+  const float *Ad, *Bd, *gd, *x0, *xref;  /* as cmpc_solve */
+  const uint8_t* contact;
+  const float *mu, *fz_min; /* [B] nullable: the plan's constants */
+  const float *Q, *R;       /* [B][12] nullable */
+  const float* w;           /* [B][24N] nullable: the point whose held faces define w* */
+  const uint8_t* faces;     /* [B][N][4] nullable: held faces given by the caller */
+  float face_tol;           /* used when faces == NULL; 0 selects 1e-6 */
+  const float* d_x0;        /* [B][12] nullable, as every tangent */
+  const float* d_xref;      /* [B][N][12] */
+  const float* d_gd;        /* [B][12] */
+  const float* d_Q;         /* [B][12] */
+  const float* d_R;         /* [B][12] */
+  const float* d_mu;        /* [B] */
+  const float* d_fz_min;    /* [B] */
+  const float* d_Ad;        /* [B][12][12] */
+  const float* d_Bd;        /* [B][N][12][12] */
+  double* dw;               /* [B][24N] out, required */
+} cmpc_jvp_io;
+int cmpc_jvp_run(cmpc_plan* plan, int64_t B, const cmpc_jvp_io* io, void* stream);
+
 /* Certified float64 refinement of B solved instances, on the device: a primal-dual active-set
  * loop around cmpc_gain_io's u_star that replaces an answer only when the float64 KKT conditions
  * hold on the whole QP, and reports how far the answer given was from that optimum.
