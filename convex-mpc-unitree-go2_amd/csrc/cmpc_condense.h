@@ -445,21 +445,29 @@ template <class SM>
 __device__ __forceinline__ bool nilpotent_step(SM& s) {
   const int lane = opaque_lane();
   WSYNC();
+  // Lane 4 i + c (i < 12, c < 3) takes the elements (i, 4 c .. 4 c + 3) of N^2: row i of A once
+  // and the four entries of every row k, all as 16-byte reads (15 per lane, one trip; an element
+  // per lane took 24 four-byte reads in each of three trips).  Every element is the same
+  // products summed over k ascending.
+  const int i = lane >> 2, c = lane & 3;
   bool nz = false;
+  if (lane < 48 && c < 3) {
+    f4 ni[3];
 #pragma unroll
-  for (int e0 = 0; e0 < 144; e0 += 64) {
-    const int e = e0 + lane;
-    if (e < 144) {
-      const int i = e / 12, j = e % 12;
-      float acc = 0.f;
+    for (int q = 0; q < 3; ++q) {
+      ni[q] = *reinterpret_cast<const f4*>(&s.A[12 * i + 4 * q]);
 #pragma unroll
-      for (int k = 0; k < 12; ++k) {
-        const float nik = s.A[i * 12 + k] - ((i == k) ? 1.f : 0.f);
-        const float nkj = s.A[k * 12 + j] - ((k == j) ? 1.f : 0.f);
-        acc = fmaf(nik, nkj, acc);
-      }
-      nz |= acc != 0.f;
+      for (int j = 0; j < 4; ++j) ni[q][j] -= (i == 4 * q + j) ? 1.f : 0.f;
     }
+    f4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+      const f4 nk = *reinterpret_cast<const f4*>(&s.A[12 * k + 4 * c]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        acc[j] = fmaf(ni[k >> 2][k & 3], nk[j] - ((k == 4 * c + j) ? 1.f : 0.f), acc[j]);
+    }
+    nz = acc[0] != 0.f || acc[1] != 0.f || acc[2] != 0.f || acc[3] != 0.f;
   }
   return __any(nz) == 0;
 }

@@ -80,9 +80,10 @@ __device__ __forceinline__ void build_admm_basis(Smem<NC>& s, const KParams& P,
       for (int r = 0; r < 12; ++r) s.Bt[(3 * lane + a) * kBS + r] = bv[3 * r + a];
     }
   }
-  for (int p = lane; p < NC; p += 64) {
+  // param p = 3 t + a, and a trip adds 64 = 21 x 3 + 1: (t, a) are stepped along with p
+  int t = lane / 3, a = lane - 3 * t;
+  for (int p = lane; p < NC; p += 64, t += 21 + (a == 2), a = (a == 2) ? 0 : a + 1) {
     if (p < n) {
-      const int t = p / 3, a = p % 3;
       const int kl = s.tri[t];
       s.Rt[p] = s.R2[3 * (kl & 3) + a];
       s.par[p] = kl >> 2;
@@ -180,23 +181,39 @@ __device__ __forceinline__ int polish_setup(Smem<NC>& s, const KParams& P, const
     s.fpk[lane] = px | (py << 8) | (pz << 16);
   }
   WSYNC();
+  const unsigned long long sm = __ballot(lane < 4 * N && s.tri_of[lane] >= 0);
   {  // off[kk] = params of the triples before step kk = the scan base of the first triple of
      // step >= kk (its index: popcount of the stance mask below step kk), nr past the last
-    const unsigned long long sm = __ballot(lane < 4 * N && s.tri_of[lane] >= 0);
     const unsigned long long below = (lane >= 16) ? ~0ull : ((1ull << (4 * lane)) - 1ull);
     const int tstar = __popcll(sm & below);
     const int bt = __shfl(base, tstar < 64 ? tstar : 63, 64);
     if (lane <= N) s.off[lane] = (tstar < ntri) ? bt : nr;
   }
-  for (int o = lane; o < 12 * N; o += 64) {  // d~ = d + B t0 (LDS only)
-    const int kk = o / 12, r = o % 12;
-    float acc = s.D[o];
+  {  // d~ = d + B t0 (LDS only).  Entry o = 12 kk + r, and a trip adds 64 = 5 x 12 + 4: (kk, r) are
+     // stepped along with o.  The triple of (kk, leg) is the count of stance pairs before it in
+     // the stance mask, and whether it locks fz is its bit of the wave's ballot of `zl`: what
+     // s.tri_of and s.code hold, without their two dependent reads per leg.  The locked triples'
+     // terms are added over the legs ascending as before.
+    const unsigned long long zm = __ballot(zl);
+    int kk = lane / 12, r = lane - 12 * kk;
+    for (int o = lane; o < 12 * N; o += 64) {
+      float acc = s.D[o];
+      const unsigned m4 = (unsigned)(sm >> (4 * kk)) & 15u;
+      int t = __popcll(sm & ((1ull << (4 * kk)) - 1ull));
 #pragma unroll
-    for (int l = 0; l < 4; ++l) {
-      const int t = s.tri_of[4 * kk + l];
-      if (t >= 0 && (s.code[t] & 1)) acc += s.G[t * 12 + r];
+      for (int l = 0; l < 4; ++l) {
+        const bool st = ((m4 >> l) & 1u) != 0;
+        if (st && ((zm >> t) & 1ull)) acc += s.G[t * 12 + r];
+        t += st ? 1 : 0;
+      }
+      s.Dt[o] = acc;
+      r += 4;
+      kk += 5;
+      if (r >= 12) {
+        r -= 12;
+        ++kk;
+      }
     }
-    s.Dt[o] = acc;
   }
   for (int p = lane; p < NC; p += 64)
     if (p >= nr) s.v[p] = 0.f;

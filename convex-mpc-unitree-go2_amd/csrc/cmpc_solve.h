@@ -208,13 +208,29 @@ __device__ __forceinline__ void stage_instance(Smem<NC>& s, const KParams& P, co
   if (lane < 4 * N) s.tri_of[lane] = stc ? pos : -1;
   WSYNC();
   {
-    for (int o = lane; o < NP; o += 64) {  // d_k = A r_k + gd - r_{k+1}, r_0 = x0
-      const int k = o / 12, r = o % 12;
-      const float* rk = &s.G[12 * k];
-      float acc = s.G[256 + r] - rk[12 + r];
+    // d_k = A r_k + gd - r_{k+1}, r_0 = x0.  Entry o = 12 k + r, and a trip adds 64 = 5 x 12 + 4:
+    // (k, r) are stepped along with o.  Row r of A and r_k are 16-byte aligned 12-float rows,
+    // read as three f4 each; the sum runs over j ascending as before.
+    static_assert(offsetof(Smem<NC>, A) % 16 == 0 && offsetof(Smem<NC>, G) % 16 == 0,
+                  "the rows of A and r_k are read as f4");
+    int k = lane / 12, r = lane - 12 * k;
+    for (int o = lane; o < NP; o += 64) {
+      const f4* ar = reinterpret_cast<const f4*>(&s.A[12 * r]);
+      const f4* rk = reinterpret_cast<const f4*>(&s.G[12 * k]);
+      float acc = s.G[256 + r] - s.G[12 * k + 12 + r];
 #pragma unroll
-      for (int j = 0; j < 12; ++j) acc = fmaf(s.A[r * 12 + j], rk[j], acc);
+      for (int q = 0; q < 3; ++q) {
+        const f4 av = ar[q], rv = rk[q];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc = fmaf(av[j], rv[j], acc);
+      }
       s.D[o] = acc;
+      r += 4;
+      k += 5;
+      if (r >= 12) {
+        r -= 12;
+        ++k;
+      }
     }
     build_admm_basis<NC>(s, P, Bg, ntri, &bw, __ballot(stc));
   }

@@ -39,6 +39,17 @@ FUNCS = {
     "polish_check": ("cmpc_polish.h", "polish_check"),
     "polish_setup": ("cmpc_polish.h", "polish_setup"),
     "stage_instance": ("cmpc_solve.h", "stage_instance"),
+    # what an instance runs once, or once per polish session
+    "build_admm_basis": ("cmpc_polish.h", "build_admm_basis"),
+    "nilpotent_step": ("cmpc_condense.h", "nilpotent_step"),
+    "starting_point": ("cmpc_solve.h", "starting_point"),
+    "solve_instance": ("cmpc_solve.h", "solve_instance"),
+    "drain_bin": ("cmpc_solve.h", "drain_bin"),
+    "instance_terrain": ("cmpc_instance.h", "instance_terrain"),
+    "force_triple": ("cmpc_solve.h", "output writers"),
+    "write_w": ("cmpc_solve.h", "output writers"),
+    "write_y": ("cmpc_solve.h", "output writers"),
+    "write_lam": ("cmpc_solve.h", "output writers"),
 }
 
 
