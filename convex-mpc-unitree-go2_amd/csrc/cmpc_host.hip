@@ -259,6 +259,9 @@ int cmpc_plan_create(const cmpc_params* p, cmpc_plan** out) {
   if (!(p->mu > 0.f) || !std::isfinite(p->mu)) return fail(CMPC_E_INVALID, "cmpc_plan_create: mu must be > 0");
   if (!std::isfinite(p->fz_min)) return fail(CMPC_E_INVALID, "cmpc_plan_create: fz_min must be finite");
   if (p->max_iter < 1) return fail(CMPC_E_INVALID, "cmpc_plan_create: max_iter must be >= 1");
+  if (!(p->eps_abs >= 0.f) || !std::isfinite(p->eps_abs) || !(p->eps_rel >= 0.f) ||
+      !std::isfinite(p->eps_rel))
+    return fail(CMPC_E_INVALID, "cmpc_plan_create: eps_abs and eps_rel must be finite and >= 0");
   if (!(p->rho > 0.f) || !(p->sigma >= 0.f) || !(p->alpha > 0.f && p->alpha < 2.f))
     return fail(CMPC_E_INVALID, "cmpc_plan_create: need rho > 0, sigma >= 0, 0 < alpha < 2");
   if (p->polish_stable < 1 || p->polish_refine < 1 || !(p->polish_tol > 0.f) ||

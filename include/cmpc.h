@@ -47,7 +47,23 @@
  *                                     2 solved inaccurate: ADMM residuals within eps, or a polished
  *                                       point that misses the certified bound (returned, but not
  *                                       verified to 1e-4),
- *                                     -2 max iterations, -10 numerical failure or an invalid
+ *                                     -2 max iterations.
+ *                                       There is no residual-based early stop: an instance ends
+ *                                       through a polish or at max_iter, so status 2 can only be
+ *                                       returned at iters == max_iter or for a polished point
+ *                                       that misses the bound.  At max_iter without an accepted
+ *                                       polish the forces returned are ADMM's z, and the status
+ *                                       is 2 when rp <= eps_abs + eps_rel np and
+ *                                       rd <= eps_abs + eps_rel nd, else -2, on the last
+ *                                       iteration's values of (infinity norms over the stance
+ *                                       forces; x, z, y after that iteration's updates, g the
+ *                                       gradient P x + q of the condensed cost at the x the
+ *                                       iteration started from)
+ *                                         rp = |x - z|,  np = max(|x|, |z|),
+ *                                         rd = |g + y|,  nd = max(|g|, |y|).
+ *                                       These are this solver's definitions, not OSQP's (whose
+ *                                       dual scale is max(|P x|, |q|, |y|)).
+ *                                     -10 numerical failure or an invalid
  *                                       per-instance mu / fz_min entry or Q / R row
  *                                       (cmpc_solve_io)
  *   iters   [B]                int32  ADMM iterations taken
@@ -86,14 +102,20 @@ typedef struct cmpc_params {
   float R[12];            /* input weight diagonal (centroidal_mpc.py:13) */
   float mu;               /* friction coefficient (centroidal_mpc.py:15) */
   float fz_min;           /* stance normal-force lower bound (centroidal_mpc.py:127) */
-  float eps_abs;          /* ADMM residual tolerances for status 2 (OPTS eps_abs/eps_rel) */
+  float eps_abs;          /* ADMM residual tolerances for status 2 (OPTS eps_abs/eps_rel), both
+                             finite and >= 0; the test is stated under `status` above */
   float eps_rel;
   int32_t max_iter;       /* ADMM iteration cap (OPTS max_iter) */
-  float rho;              /* initial ADMM penalty (the NC = 128 bin starts at rho / 2 and returns
-                             to rho after a failed polish session) */
+  float rho;              /* initial ADMM penalty (the bins with more than 96 free forces start
+                             at rho / 2 and return to rho after a failed polish session; a free
+                             force is one axis of a stance (step, leg) pair) */
   float sigma;            /* ADMM proximal regularisation (OSQP sigma) */
   float alpha;            /* over-relaxation (OSQP alpha) */
-  int32_t adaptive_rho_interval; /* iterations between rho updates (0 = off) */
+  int32_t adaptive_rho_interval; /* iterations between rho updates (0 = off).  At an iteration
+                             that is a multiple of it and not the last (iteration < max_iter),
+                             with rp, rd, np, nd of that iteration as defined under `status`:
+                             rho' = clip(rho sqrt((rp / np) / (rd / nd)), 1e-6, 1e6), taken (and
+                             the matrix factorized anew) when rho' > 5 rho or rho' < rho / 5 */
   int32_t polish_stable;  /* polish after the active set is unchanged this many iterations */
   int32_t polish_refine;  /* refinement steps inside the polish before its convergence test may
                              stop them (up to 4 more while the step still halves); default 2

@@ -618,7 +618,10 @@ def solve(inst, p: Params):
         if p.adaptive_interval and it % p.adaptive_interval == 0:
             rp = np.max(np.abs(x - z)); rd = np.max(np.abs(g + y))
             npn = max(np.max(np.abs(x)), np.max(np.abs(z)), 1e-30)
-            # OSQP normalisation max(|P x|, |q|, |y|), with |P x| <= |g| + |q| approximated
+            # OSQP normalisation max(|P x|, |q|, |y|), with |P x| <= |g| + |q| approximated.
+            # The model keeps this extra |q| term; the kernel does not: its dual scale is
+            # nd = max(|g|, |y|) (include/cmpc.h under `status`; tests/admm_ref.py is the
+            # reference of the kernel's formula), so the two can adapt rho differently.
             nd = max(np.max(np.abs(g)), nq, np.max(np.abs(y)), 1e-30)
             nr = rho * np.sqrt((rp / npn) / (rd / nd + 1e-30))
             nr = min(max(nr, 1e-6), 1e6)

@@ -167,7 +167,9 @@ def test_last_iteration(params, mode):
     must first stay unchanged for polish_stable = 3 iterations, and the last iteration starts
     none); in the second case the last iteration is also one at which rho would adapt.  Every
     instance (each has stance legs) returns status 2 or -2 at iters == max_iter, finite, with
-    states that are the rollout of its forces."""
+    states that are the rollout of its forces.  Which of the two statuses is right, and the
+    iterates themselves, are checked against the float64 reference in
+    tests/test_gpu_admm_iterates.py (test_exit_status, test_iterates_default)."""
     from cmpc import solve_batch
     b = batch(16)
     w, st, it = solve_batch(b, plan=_plan(mode, **params))
