@@ -93,6 +93,32 @@ class CRefineIO(ctypes.Structure):
                           "info", "res", "w64", "lam_out", "faces_out", "w_out", "status")
 
 
+def _dynamics_io_fields(*names):
+    """``size``, cmpc_build_dynamics' four inputs and ``dt``, then the named fields."""
+    head = ("mass", "inertia", "r_feet", "xref")
+    return ([("size", ctypes.c_uint32)] + [(n, ctypes.c_void_p) for n in head] +
+            [("dt", ctypes.c_float)] + [(n, ctypes.c_void_p) for n in names])
+
+
+class CDynamicsVjpIO(ctypes.Structure):
+    """cmpc_dynamics_vjp_io (include/cmpc.h): a batch of robots whose gradients through the
+    dynamics builder are wanted, given dL/dAd and dL/dBd.  ``size`` is this mirror's sizeof."""
+    _fields_ = _dynamics_io_fields("g_Ad", "g_Bd", "g_mass", "g_inertia", "g_r_feet", "g_yaw")
+
+
+class CDynamicsJvpIO(ctypes.Structure):
+    """cmpc_dynamics_jvp_io (include/cmpc.h): a batch of robots whose forward-mode derivative of
+    the dynamics builder is wanted, given the tangents of its inputs.  ``size`` is this mirror's
+    sizeof."""
+    _fields_ = _dynamics_io_fields("d_mass", "d_inertia", "d_r_feet", "d_xref", "d_Ad", "d_Bd")
+
+
+# Plan.dynamics_vjp's results (field g_<name> of cmpc_dynamics_vjp_io; yaw: the mean reference yaw)
+DYNAMICS_VJP_OUTPUTS = ("mass", "inertia", "r_feet", "yaw")
+# Plan.dynamics_jvp's tangents (field d_<name> of cmpc_dynamics_jvp_io) and results
+DYNAMICS_JVP_TANGENTS = ("mass", "inertia", "r_feet", "xref")
+DYNAMICS_JVP_OUTPUTS = ("Ad", "Bd")
+
 # cmpc_refine_io's info values below zero (CMPC_REFINE_*) and the results Plan.refine can return
 REFINE_INVALID, REFINE_ROUNDS, REFINE_CYCLE, REFINE_MAX_ROUNDS = -1, -2, -3, 16
 REFINE_OUTPUTS = ("info", "res", "w64", "lam", "faces")
@@ -146,7 +172,9 @@ def _prototypes() -> dict:
     # the struct entries: (plan, B, const io*, stream)
     for name, io in (("cmpc_solve_io_run", CSolveIO), ("cmpc_kkt_run", CKktIO),
                      ("cmpc_gain_run", CGainIO), ("cmpc_vjp_run", CVjpIO),
-                     ("cmpc_refine_run", CRefineIO), ("cmpc_jvp_run", CJvpIO)):
+                     ("cmpc_refine_run", CRefineIO), ("cmpc_jvp_run", CJvpIO),
+                     ("cmpc_dynamics_vjp_run", CDynamicsVjpIO),
+                     ("cmpc_dynamics_jvp_run", CDynamicsJvpIO)):
         table[name] = ([vp, i64, ptr(io), vp], rc)
     return table
 

@@ -7,6 +7,11 @@ launch (cmpc_jvp_run) for the inputs that carry a tangent.  The ``torch.func`` t
 ``Function`` wrapped tensors without storage, which a native launch cannot take: ``jvp(plan, ...,
 tangents)`` below is the functional form for them.
 
+``build_dynamics(plan, ...)`` is :meth:`cmpc.Plan.build_dynamics` whose ``Ad`` and ``Bd`` carry a
+gradient in the mass, the inertia, the foot levers and the reference yaw (one
+:meth:`cmpc.Plan.dynamics_vjp` or :meth:`cmpc.Plan.dynamics_jvp` launch): chained
+into ``solve``, a loss on the solution reaches the quantities the dynamics are built from.
+
 The gradient is that of the fp64 optimum on the faces of the friction pyramid the returned
 ``w`` holds, with that face set fixed -- the function :meth:`cmpc.Plan.gain` solves -- not of the
 fp32 ``w`` itself: the two differ by the solver's tolerance, and where ``w`` sits within
@@ -85,6 +90,76 @@ def solve(plan, Ad, Bd, gd, x0, xref, contact, mu=None, fz_min=None, Q=None, R=N
     inputs that carry a tangent, cast to ``w``'s dtype, zero in the rows of status -10.  See the
     module's note on which function the derivative belongs to."""
     return _Solve.apply(plan, face_tol, Ad, Bd, gd, x0, xref, contact, mu, fz_min, Q, R)
+
+
+_DYNAMICS = ("mass", "inertia", "r_feet", "xref")    # positions 2..5 of _BuildDynamics' inputs
+
+
+class _BuildDynamics(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, dt, mass, inertia, r_feet, xref):
+        Ad, Bd, gd = plan.build_dynamics(mass, inertia, r_feet, xref, dt)
+        ctx.plan, ctx.dt = plan, dt
+        ctx.save_for_backward(mass, inertia, r_feet, xref)
+        ctx.save_for_forward(mass, inertia, r_feet, xref)
+        ctx.mark_non_differentiable(gd)     # a constant of dt
+        ctx.set_materialize_grads(False)    # an output nothing reads arrives as None
+        return Ad, Bd, gd
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_Ad, g_Bd, _g_gd):
+        inputs = ctx.saved_tensors
+        need = dict(zip(_DYNAMICS, ctx.needs_input_grad[2:]))
+        want = [n if n != "xref" else "yaw" for n in _DYNAMICS if need[n]]
+        grads = [None] * 6
+        if not want or (g_Ad is None and g_Bd is None):
+            return tuple(grads)
+        f64 = torch.float64
+        # (Plan.dynamics_vjp launches on torch's current stream)
+        res = ctx.plan.dynamics_vjp(*inputs, ctx.dt,
+                                    g_Ad=None if g_Ad is None else g_Ad.to(f64).contiguous(),
+                                    g_Bd=None if g_Bd is None else g_Bd.to(f64).contiguous(),
+                                    want=want)
+        for pos, (n, t) in enumerate(zip(_DYNAMICS, inputs)):
+            if n == "xref" and "yaw" in res:            # the mean's gradient, spread over the steps
+                g = torch.zeros_like(t)
+                g[:, :, 5] = (res["yaw"] / t.shape[1]).to(t.dtype)[:, None]
+                grads[2 + pos] = g
+            elif n in res:
+                grads[2 + pos] = res[n].to(t.dtype)
+        return tuple(grads)
+
+    @staticmethod
+    def jvp(ctx, _plan, _dt, *tangents):
+        inputs = ctx.saved_tensors
+        given = {n: t.detach().to(torch.float32).contiguous()
+                 for n, t in zip(_DYNAMICS, tangents) if t is not None}
+        if not given:
+            return None, None, None
+        # (Plan.dynamics_jvp launches on torch's current stream)
+        res = ctx.plan.dynamics_jvp(*inputs, ctx.dt, given)
+        return res["Ad"], res["Bd"], None
+
+
+def build_dynamics(plan, mass, inertia, r_feet, xref, dt):
+    """:meth:`cmpc.Plan.build_dynamics` -> ``(Ad, Bd, gd)`` with ``Ad`` and ``Bd``
+    differentiable in ``mass``, ``inertia``, ``r_feet`` and ``xref`` (through the mean of its yaw
+    column, which sets the rotation of the dynamics): chained into :func:`solve`, a loss on the
+    solution is differentiable on the device in mass, inertia, footholds and reference yaw.
+    The backward pass is one :meth:`cmpc.Plan.dynamics_vjp` launch for exactly the inputs that
+    need a gradient, on the current stream: the incoming gradients are cast to float64, the
+    yaw gradient is spread as ``g_yaw / N`` into column 5 of an otherwise zero ``xref`` gradient,
+    and the float64 results are cast to each input's dtype.  Under forward-mode AD the tangents
+    of ``Ad`` and ``Bd`` are one :meth:`cmpc.Plan.dynamics_jvp` launch for exactly the inputs
+    that carry a tangent.  ``gd`` is a constant of ``dt``: it carries no gradient and its tangent
+    is zero.  The derivative is that of the closed form in fp64 on the fp32 inputs, first order
+    only (a second backward raises), and there is none in ``dt``.
+
+    Composed with :func:`solve`, ``g_Ad`` and ``g_Bd`` pass through fp32 on their way here (the
+    dtype of ``Ad`` and ``Bd``); the chain that stays in float64 is :meth:`cmpc.Plan.vjp` with
+    ``want=("Ad", "Bd")`` -> :meth:`cmpc.Plan.dynamics_vjp`."""
+    return _BuildDynamics.apply(plan, dt, mass, inertia, r_feet, xref)
 
 
 def jvp(plan, Ad, Bd, gd, x0, xref, contact, tangents, mu=None, fz_min=None, Q=None, R=None,

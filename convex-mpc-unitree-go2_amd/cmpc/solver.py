@@ -118,6 +118,19 @@ def _dynamics_spec(B, N) -> tuple:
 
 
 @_spec
+def _dynamics_grad_spec(B, N) -> tuple:
+    """(gradients in, gradients out, tangents in, tangents out) of cmpc_dynamics_vjp_run and
+    cmpc_dynamics_jvp_run; the two results are name -> (io field, dtype, shape)."""
+    f32, f64 = torch.float32, torch.float64
+    inputs, outputs = _dynamics_spec(B, N)
+    return (dict(g_Ad=(f64, (B, 12, 12)), g_Bd=(f64, (B, N, 12, 12))),
+            dict(mass=("g_mass", f64, (B,)), inertia=("g_inertia", f64, (B, 3, 3)),
+                 r_feet=("g_r_feet", f64, (B, N, 4, 3)), yaw=("g_yaw", f64, (B,))),
+            {"d_" + n: s for n, s in inputs.items()},
+            {n: ("d_" + n, *outputs[n]) for n in _lib.DYNAMICS_JVP_OUTPUTS})
+
+
+@_spec
 def _traj_spec(B, N) -> tuple:
     """(inputs, results) of cmpc_generate_traj."""
     f32, f64, p = torch.float32, torch.float64, _problem_spec(B, N)
@@ -610,6 +623,85 @@ class Plan:
         B = mass.shape[0]
         return self._pipeline("cmpc_build_dynamics", _dynamics_spec(B, self.params.N),
                               (mass, inertia, r_feet, xref), out, stream, lambda *p: (B, dt, *p))
+
+    def dynamics_vjp(self, mass, inertia, r_feet, xref, dt, g_Ad=None, g_Bd=None, want=None,
+                     out=None, stream=None):
+        """Gradients of a loss through :meth:`build_dynamics` on the device
+        (cmpc_dynamics_vjp_run, include/cmpc.h): from dL/dAd and dL/dBd to the gradients in the
+        mass, the world-frame inertia, the foot levers and the mean reference yaw.
+
+        ``mass`` .. ``xref`` and ``dt`` as for :meth:`build_dynamics`; ``g_Ad`` (B, 12, 12) and
+        ``g_Bd`` (B, N, 12, 12) are float64 device tensors -- what :meth:`vjp` returns for
+        ``want=("Ad", "Bd")`` -- of which one may be None (zeros).  ``want`` names the results, a
+        non-empty subset of ``("mass", "inertia", "r_feet", "yaw")`` (None: all four); a result
+        does not depend on what else is asked for, and the parts of ``g_Bd`` that only the
+        others need are not read.  Returns a dict of float64 device tensors: ``mass`` (B,),
+        ``inertia`` (B, 3, 3) with its nine entries independent, ``r_feet`` (B, N, 4, 3) and
+        ``yaw`` (B,), the gradient in the mean of ``xref[:, :, 5]`` -- every ``xref[b, k, 5]``
+        gets ``yaw[b] / N``, every other entry of ``xref`` zero.  The gradient is that of the
+        closed form in fp64 on the fp32 inputs, not of its fp32-rounded outputs.  ``out`` is a
+        dict of preallocated tensors for some or all of the wanted names.  Asynchronous on
+        ``stream`` (default: torch's current stream), no allocation when every wanted name is in
+        ``out``, graph-capturable; B is not limited by max_batch."""
+        self._need("cmpc_dynamics_vjp_run", "dynamics_vjp")
+        want = _lib.DYNAMICS_VJP_OUTPUTS if want is None else tuple(want)
+        unknown = [n for n in want if n not in _lib.DYNAMICS_VJP_OUTPUTS]
+        if unknown or not want:
+            raise ValueError(f"dynamics_vjp: want {want} must be a non-empty subset of "
+                             f"{_lib.DYNAMICS_VJP_OUTPUTS}")
+        if g_Ad is None and g_Bd is None:
+            raise ValueError("dynamics_vjp needs g_Ad or g_Bd: one must be given")
+        B = mass.shape[0]
+        N = self.params.N
+        grads, results, _, _ = _dynamics_grad_spec(B, N)
+        io = _lib.CDynamicsVjpIO()
+        io.size = ctypes.sizeof(_lib.CDynamicsVjpIO)
+        self._fill_io(io, _dynamics_spec(B, N)[0],
+                      dict(mass=mass, inertia=inertia, r_feet=r_feet, xref=xref), {})
+        self._fill_io(io, grads, {}, dict(g_Ad=g_Ad, g_Bd=g_Bd))
+        res = self._results(io, results, want, (), out, self.device)
+        io.dt = float(dt)
+        self._run_io("cmpc_dynamics_vjp_run", io, B, stream)
+        return res
+
+    def dynamics_jvp(self, mass, inertia, r_feet, xref, dt, tangents, want=("Ad", "Bd"), out=None,
+                     stream=None):
+        """Forward-mode derivative of :meth:`build_dynamics` on the device
+        (cmpc_dynamics_jvp_run, include/cmpc.h): how ``Ad`` and ``Bd`` move with the mass, the
+        inertia, the foot levers and the reference yaw.
+
+        ``mass`` .. ``xref`` and ``dt`` as for :meth:`build_dynamics`.  ``tangents`` is a
+        non-empty dict from input name, one of ``("mass", "inertia", "r_feet", "xref")``, to an
+        fp32 device tensor of that input's shape; an input that is not named does not move, and
+        of ``xref``'s tangent only column 5 (the yaw) is read.  ``want`` is a non-empty subset of
+        ``("Ad", "Bd")``.  Returns a dict of fp32 device tensors of those shapes, the fp64
+        derivative rounded once -- what :meth:`jvp` takes as its ``Ad`` and ``Bd`` tangents;
+        ``Ad`` is exactly zero outside its rows 3-4, columns 9-10, and ``gd`` does not move.  A
+        result does not depend on whether the other is asked for.  ``out`` is a dict of
+        preallocated tensors for some or all of the wanted names.  Asynchronous on ``stream``
+        (default: torch's current stream), no allocation when every wanted name is in ``out``,
+        graph-capturable; B is not limited by max_batch."""
+        self._need("cmpc_dynamics_jvp_run", "dynamics_jvp")
+        tangents, want = dict(tangents), tuple(want)
+        unknown = [n for n in tangents if n not in _lib.DYNAMICS_JVP_TANGENTS]
+        if unknown or not tangents:
+            raise ValueError(f"dynamics_jvp: tangents {tuple(tangents)} must name a non-empty "
+                             f"subset of {_lib.DYNAMICS_JVP_TANGENTS}")
+        if not want or [n for n in want if n not in _lib.DYNAMICS_JVP_OUTPUTS]:
+            raise ValueError(f"dynamics_jvp: want {want} must be a non-empty subset of "
+                             f"{_lib.DYNAMICS_JVP_OUTPUTS}")
+        B = mass.shape[0]
+        N = self.params.N
+        _, _, moves, results = _dynamics_grad_spec(B, N)
+        io = _lib.CDynamicsJvpIO()
+        io.size = ctypes.sizeof(_lib.CDynamicsJvpIO)
+        self._fill_io(io, _dynamics_spec(B, N)[0],
+                      dict(mass=mass, inertia=inertia, r_feet=r_feet, xref=xref), {})
+        self._fill_io(io, moves, {"d_" + n: t for n, t in tangents.items()}, {})
+        res = self._results(io, results, want, (), out, self.device)
+        io.dt = float(dt)
+        self._run_io("cmpc_dynamics_jvp_run", io, B, stream)
+        return res
 
     def generate_traj(self, x0, pos_des, cmd, t_now, gait, foot_lever, hip, dt, out=None,
                       stream=None):

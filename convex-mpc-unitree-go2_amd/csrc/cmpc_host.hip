@@ -24,6 +24,7 @@
 #include "cmpc_vjp.hip"       // gradients of a loss through the optimum on the held faces
 #include "cmpc_refine.hip"    // certified float64 refinement around the optimum on the held faces
 #include "cmpc_jvp.hip"       // forward-mode derivatives of the optimum on the held faces
+#include "cmpc_dynamics_grad.hip"  // reverse- and forward-mode derivatives of the dynamics builder
 
 constexpr int kNumGroups = 3;  // solve kernels (register classes), see solve_group_kernel
 static_assert(kNumGroups == CMPC_NUM_SOLVE_KERNELS, "one timing slot per solve kernel");
@@ -209,6 +210,20 @@ int check_pipeline(const cmpc_plan* pl, const char* what, bool negative,
   if (!pl) return fail(CMPC_E_INVALID, std::string(what) + ": null plan");
   if (int rc = check_device(pl, what)) return rc;
   if (negative) return fail(CMPC_E_INVALID, std::string(what) + msg);
+  return CMPC_OK;
+}
+
+// the checks of the two derivative entries of the dynamics builder after io_copy, in
+// cmpc_build_dynamics' order.  `inputs`: its four arrays are there; `missing`: the message of a
+// failed check that ranks after them, or NULL.  B == 0 passes (the caller returns before a launch).
+int check_dynamics_grad(const cmpc_plan* pl, int64_t B, float dt, bool inputs, const char* missing,
+                        const char* what) {
+  const std::string w(what);
+  if (int rc = check_pipeline(pl, what, B < 0)) return rc;
+  if (!(dt > 0.f) || !std::isfinite(dt)) return fail(CMPC_E_INVALID, w + ": dt must be > 0");
+  if (B == 0) return CMPC_OK;
+  if (!inputs) return fail(CMPC_E_INVALID, w + ": null array argument");
+  if (missing) return fail(CMPC_E_INVALID, w + missing);
   return CMPC_OK;
 }
 
@@ -719,6 +734,47 @@ int cmpc_build_dynamics(cmpc_plan* pl, int64_t B, float dt, const float* mass,
   // (grid-stride: ~32 resident waves per CU)
   return launch(cmpc::dynamics_kernel, "dynamics_kernel launch", grid_stride_blocks(B), 64, 0, stream,
                 pl->kp.N, (double)dt, B, mass, inertia, r_feet, xref, Ad, Bd, gd);
+}
+
+int cmpc_dynamics_vjp_run(cmpc_plan* pl, int64_t B, const cmpc_dynamics_vjp_io* io, void* stream) {
+  const char* what = "cmpc_dynamics_vjp_run";
+  cmpc_dynamics_vjp_io a;
+  if (int rc = io_copy(io, offsetof(cmpc_dynamics_vjp_io, g_mass) + sizeof(io->g_mass), what,
+                       "cmpc_dynamics_vjp_io", a))
+    return rc;
+  if (int rc = check_dynamics_grad(
+          pl, B, a.dt, a.mass && a.inertia && a.r_feet && a.xref,
+          !a.g_Ad && !a.g_Bd ? ": g_Ad and g_Bd are both null (one must be given)"
+          : !a.g_mass && !a.g_inertia && !a.g_r_feet && !a.g_yaw
+              ? ": every output is null (one must be given)"
+              : nullptr,
+          what))
+    return rc;
+  if (B == 0) return CMPC_OK;
+  const cmpc::DynVjpArgs k{a.mass, a.inertia, a.r_feet, a.xref, a.g_Ad, a.g_Bd,
+                           a.g_mass, a.g_inertia, a.g_r_feet, a.g_yaw};
+  return launch(cmpc::vjp_dynamics_kernel, "vjp_dynamics_kernel launch", grid_stride_blocks(B), 64,
+                0, stream, pl->kp.N, (double)a.dt, B, k);
+}
+
+int cmpc_dynamics_jvp_run(cmpc_plan* pl, int64_t B, const cmpc_dynamics_jvp_io* io, void* stream) {
+  const char* what = "cmpc_dynamics_jvp_run";
+  cmpc_dynamics_jvp_io a;
+  if (int rc = io_copy(io, offsetof(cmpc_dynamics_jvp_io, d_Ad) + sizeof(io->d_Ad), what,
+                       "cmpc_dynamics_jvp_io", a))
+    return rc;
+  if (int rc = check_dynamics_grad(
+          pl, B, a.dt, a.mass && a.inertia && a.r_feet && a.xref,
+          !a.d_mass && !a.d_inertia && !a.d_r_feet && !a.d_xref
+              ? ": every tangent is null (one must be given)"
+          : !a.d_Ad && !a.d_Bd ? ": d_Ad and d_Bd are both null (one must be given)" : nullptr,
+          what))
+    return rc;
+  if (B == 0) return CMPC_OK;
+  const cmpc::DynJvpArgs k{a.mass, a.inertia, a.r_feet, a.xref, a.d_mass, a.d_inertia,
+                           a.d_r_feet, a.d_xref, a.d_Ad, a.d_Bd};
+  return launch(cmpc::jvp_dynamics_kernel, "jvp_dynamics_kernel launch", grid_stride_blocks(B), 64,
+                0, stream, pl->kp.N, (double)a.dt, B, k);
 }
 
 int cmpc_generate_traj(cmpc_plan* pl, int64_t B, double dt, const float* x0, double* pos_des,

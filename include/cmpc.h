@@ -587,6 +587,86 @@ int cmpc_build_dynamics(cmpc_plan* plan, int64_t B, float dt, const float* mass,
                         const float* inertia, const float* r_feet, const float* xref,
                         float* Ad, float* Bd, float* gd, void* stream);
 
+/* Gradients of a loss through cmpc_build_dynamics, on the device: from dL/dAd and dL/dBd (the
+ * fp64 arrays cmpc_vjp_run writes) to dL/d(mass, inertia, r_feet, reference yaw).  The function
+ * differentiated is the closed form above evaluated in fp64 on the fp32 inputs widened exactly,
+ * not its fp32-rounded outputs.  Per robot, with h2 = dt^2/2:
+ *   minv = 1/m,  J = inertia^-1 (all 9 entries of inertia independent, no symmetrisation),
+ *   yaw = (1/N) sum_k xref[k][5],  Rt = [[c, s, 0], [-s, c, 0], [0, 0, 1]]  (c = cos yaw, s = sin yaw)
+ * and per (step k, leg l), with S = [r_kl]x, W = J S and V = Rt W, the 3x3 blocks of
+ * Bd_k[:, 3l:3l+3] are  rows 0-2 h2 minv I3,  rows 3-5 h2 V,  rows 6-8 dt minv I3,
+ * rows 9-11 dt W;  Ad[3:6, 9:12] = dt Rt.  Every other entry of Ad, and gd, is constant.
+ * With GA = g_Ad, and G0..G3 the blocks of rows 0-2, 3-5, 6-8, 9-11 of g_Bd[k][:, 3l:3l+3]:
+ *   g_minv = sum_kl (h2 tr G0 + dt tr G2),            g_mass = -g_minv / m^2
+ *   M_kl   = dt G3 + h2 Rt' G1                        (the gradient in W_kl)
+ *   g_S    = J' M_kl,   g_r_feet[k][l] = (g_S[2][1] - g_S[1][2], g_S[0][2] - g_S[2][0],
+ *                                          g_S[1][0] - g_S[0][1])
+ *   g_J    = sum_kl M_kl S',                          g_inertia = -J' g_J J'
+ *   g_Rt   = dt GA[3:6, 9:12] + h2 sum_kl G1 W_kl'
+ *   g_yaw  = -s g_Rt[0][0] + c g_Rt[0][1] - c g_Rt[1][0] - s g_Rt[1][1]
+ * The gradient in xref[b][k][5] is g_yaw[b] / N for every k, in every other entry of xref zero.
+ *   mass, inertia, r_feet, xref   as for cmpc_build_dynamics, required
+ *   dt                            > 0 and finite, else CMPC_E_INVALID
+ *   g_Ad   [B][12][12]    fp64    nullable: read as zeros
+ *   g_Bd   [B][N][12][12] fp64    nullable: read as zeros (and then not read at all); 16-byte
+ *                                 aligned; g_Ad and g_Bd both NULL: CMPC_E_INVALID
+ *   g_mass [B], g_inertia [B][3][3], g_r_feet [B][N][4][3], g_yaw [B]   fp64 outputs, each
+ *                                 nullable, at least one required (else CMPC_E_INVALID)
+ * An output is bit for bit the same whichever other outputs are asked for; the parts of g_Bd
+ * that only absent outputs need are not read.  A NULL g_Ad or g_Bd and an array of zeros give
+ * equal results (the sign of a zero may differ).  mass and inertia are not validated, as in
+ * cmpc_build_dynamics: a singular inertia gives the Inf or NaN its arithmetic gives, in that
+ * robot's rows only.
+ * `size` is the caller's sizeof of the struct (fields past it read as NULL); it must reach past
+ * `g_mass`.  B >= 0 (B == 0 returns CMPC_OK); no workspace is used, so the plan's max_batch does
+ * not limit B.  Each sum runs in a fixed order: the results are bitwise repeatable and do not
+ * depend on B or on the robot's place in the batch.  Asynchronous on `stream`, no allocation, no
+ * host synchronisation, graph-capturable; the plan's device must be current. */
+typedef struct cmpc_dynamics_vjp_io {
+  uint32_t size;            /* sizeof of this struct in the caller's header */
+  const float *mass, *inertia, *r_feet, *xref;  /* as cmpc_build_dynamics, required */
+  float dt;                 /* > 0, finite */
+  const double* g_Ad;       /* [B][12][12] nullable: read as zeros */
+  const double* g_Bd;       /* [B][N][12][12] nullable: read as zeros; one of the two required */
+  double* g_mass;           /* [B] nullable, as every output; one required */
+  double* g_inertia;        /* [B][3][3] */
+  double* g_r_feet;         /* [B][N][4][3] */
+  double* g_yaw;            /* [B] gradient in yaw_avg; d/dxref[b][k][5] = g_yaw[b] / N */
+} cmpc_dynamics_vjp_io;
+int cmpc_dynamics_vjp_run(cmpc_plan* plan, int64_t B, const cmpc_dynamics_vjp_io* io, void* stream);
+
+/* Forward-mode derivative of cmpc_build_dynamics, on the device: how Ad and Bd move with the
+ * mass, the inertia, the foot levers and the reference yaw -- cmpc_dynamics_vjp_io's function
+ * and notation, its Jacobian applied from the other side.  The tangents are fp32 of the inputs'
+ * shapes, widened exactly; of d_xref only column 5 is read:
+ *   dminv = -d_mass / m^2,   dJ = -J d_inertia J,   dyaw = (1/N) sum_k d_xref[k][5]
+ *   dRt   = dyaw [[-s, c, 0], [-c, -s, 0], [0, 0, 0]]
+ *   dS    = [d_r_kl]x,   dW = dJ S + J dS,   dV = dRt W + Rt dW
+ * the blocks of d_Bd_k[:, 3l:3l+3] are  h2 dminv I3,  h2 dV,  dt dminv I3,  dt dW, and
+ * d_Ad[3:6, 9:12] = dt dRt with every other entry of d_Ad exactly 0.  The tangent of gd is
+ * identically 0 and is not an output.
+ *   mass, inertia, r_feet, xref, dt   as in cmpc_dynamics_vjp_io
+ *   d_mass [B], d_inertia [B][3][3], d_r_feet [B][N][4][3], d_xref [B][N][12]   fp32, each
+ *                                 nullable (an input that does not move), at least one required
+ *   d_Ad   [B][12][12]    fp32    nullable output, written whole
+ *   d_Bd   [B][N][12][12] fp32    nullable output, 16-byte aligned; d_Ad and d_Bd both NULL:
+ *                                 CMPC_E_INVALID
+ * Computed in fp64 and rounded once, to the fp32 cmpc_jvp_io's d_Ad and d_Bd take.  An output is
+ * bit for bit the same whether or not the other is asked for; a NULL tangent and an array of
+ * zeros give equal results (the sign of a zero may differ).  Values are treated as in
+ * cmpc_dynamics_vjp_io.  `size` must reach past `d_Ad`; B, the fixed order of every sum, the
+ * stream, allocation and capture guarantees are cmpc_dynamics_vjp_run's. */
+typedef struct cmpc_dynamics_jvp_io {
+  uint32_t size;            /* sizeof of this struct in the caller's header */
+  const float *mass, *inertia, *r_feet, *xref;  /* as cmpc_build_dynamics, required */
+  float dt;                 /* > 0, finite */
+  const float *d_mass, *d_inertia, *d_r_feet, *d_xref;  /* the inputs' shapes, nullable, one
+                                                           required; d_xref [B][N][12] */
+  float* d_Ad;              /* [B][12][12] nullable; one of the two required */
+  float* d_Bd;              /* [B][N][12][12] */
+} cmpc_dynamics_jvp_io;
+int cmpc_dynamics_jvp_run(cmpc_plan* plan, int64_t B, const cmpc_dynamics_jvp_io* io, void* stream);
+
 /* Reference trajectory, contact table and foot levers on the device: the
  * reference's ComTraj.generate_traj (com_trajectory.py:27-207) up to the dynamics, for B robots,
  * with the Pinocchio quantities it reads passed in (see oracle/traj_ref.py):
