@@ -119,6 +119,36 @@ DYNAMICS_VJP_OUTPUTS = ("mass", "inertia", "r_feet", "yaw")
 DYNAMICS_JVP_TANGENTS = ("mass", "inertia", "r_feet", "xref")
 DYNAMICS_JVP_OUTPUTS = ("Ad", "Bd")
 
+def _traj_io_fields(*names):
+    """``size``, cmpc_generate_traj's inputs without foot_lever and ``dt``, then the named fields."""
+    head = ("x0", "pos_des", "cmd", "t_now", "gait", "hip")
+    return ([("size", ctypes.c_uint32)] + [(n, ctypes.c_void_p) for n in head] +
+            [("dt", ctypes.c_double)] + [(n, ctypes.c_void_p) for n in names])
+
+
+class CTrajVjpIO(ctypes.Structure):
+    """cmpc_traj_vjp_io (include/cmpc.h): a batch of robots whose gradients through the
+    trajectory generator are wanted, given dL/dxref, dL/dr_feet, dL/dyaw_avg and the gradient in
+    the desired position it leaves.  ``size`` is this mirror's sizeof."""
+    _fields_ = _traj_io_fields("g_xref", "g_r_feet", "g_yaw", "g_pos_des_out", "g_x0", "g_pos_des",
+                               "g_cmd", "g_foot_lever")
+
+
+class CTrajJvpIO(ctypes.Structure):
+    """cmpc_traj_jvp_io (include/cmpc.h): a batch of robots whose forward-mode derivative of the
+    trajectory generator is wanted, given the tangents of its inputs.  ``size`` is this mirror's
+    sizeof."""
+    _fields_ = _traj_io_fields("d_x0", "d_pos_des", "d_cmd", "d_foot_lever", "d_xref", "d_r_feet",
+                               "d_pos_des_out")
+
+
+# Plan.traj_vjp's results (field g_<name> of cmpc_traj_vjp_io)
+TRAJ_VJP_OUTPUTS = ("x0", "pos_des", "cmd", "foot_lever")
+# Plan.traj_jvp's tangents (field d_<name> of cmpc_traj_jvp_io) and results (pos_des: the field
+# d_pos_des_out, the tangent of the desired position cmpc_generate_traj leaves)
+TRAJ_JVP_TANGENTS = ("x0", "pos_des", "cmd", "foot_lever")
+TRAJ_JVP_OUTPUTS = ("xref", "r_feet", "pos_des")
+
 # cmpc_refine_io's info values below zero (CMPC_REFINE_*) and the results Plan.refine can return
 REFINE_INVALID, REFINE_ROUNDS, REFINE_CYCLE, REFINE_MAX_ROUNDS = -1, -2, -3, 16
 REFINE_OUTPUTS = ("info", "res", "w64", "lam", "faces")
@@ -174,7 +204,8 @@ def _prototypes() -> dict:
                      ("cmpc_gain_run", CGainIO), ("cmpc_vjp_run", CVjpIO),
                      ("cmpc_refine_run", CRefineIO), ("cmpc_jvp_run", CJvpIO),
                      ("cmpc_dynamics_vjp_run", CDynamicsVjpIO),
-                     ("cmpc_dynamics_jvp_run", CDynamicsJvpIO)):
+                     ("cmpc_dynamics_jvp_run", CDynamicsJvpIO),
+                     ("cmpc_traj_vjp_run", CTrajVjpIO), ("cmpc_traj_jvp_run", CTrajJvpIO)):
         table[name] = ([vp, i64, ptr(io), vp], rc)
     return table
 

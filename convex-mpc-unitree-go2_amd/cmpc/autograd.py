@@ -12,6 +12,12 @@ gradient in the mass, the inertia, the foot levers and the reference yaw (one
 :meth:`cmpc.Plan.dynamics_vjp` or :meth:`cmpc.Plan.dynamics_jvp` launch): chained
 into ``solve``, a loss on the solution reaches the quantities the dynamics are built from.
 
+``generate_traj(plan, ...)`` is :meth:`cmpc.Plan.generate_traj` whose ``xref``, ``r_feet`` and
+desired position carry a gradient in the state, the desired position, the velocity command and
+the current foot levers (one :meth:`cmpc.Plan.traj_vjp` or :meth:`cmpc.Plan.traj_jvp` launch,
+DESIGN.md 4u): chained into ``build_dynamics`` and ``solve``, a loss on the solution reaches the
+command, and the gradient in ``x0`` is the total one.
+
 The gradient is that of the fp64 optimum on the faces of the friction pyramid the returned
 ``w`` holds, with that face set fixed -- the function :meth:`cmpc.Plan.gain` solves -- not of the
 fp32 ``w`` itself: the two differ by the solver's tolerance, and where ``w`` sits within
@@ -160,6 +166,78 @@ def build_dynamics(plan, mass, inertia, r_feet, xref, dt):
     dtype of ``Ad`` and ``Bd``); the chain that stays in float64 is :meth:`cmpc.Plan.vjp` with
     ``want=("Ad", "Bd")`` -> :meth:`cmpc.Plan.dynamics_vjp`."""
     return _BuildDynamics.apply(plan, dt, mass, inertia, r_feet, xref)
+
+
+_TRAJ = ("x0", "pos_des", "cmd", "foot_lever")       # positions 5..8 of _GenerateTraj's inputs
+
+
+class _GenerateTraj(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, dt, t_now, gait, hip, x0, pos_des, cmd, foot_lever):
+        pos_des_out = pos_des.clone()       # the caller's stays as it is: the value before the clamp
+        xref, contact, r_feet = plan.generate_traj(x0, pos_des_out, cmd, t_now, gait, foot_lever,
+                                                   hip, dt)
+        ctx.plan, ctx.dt = plan, dt
+        ctx.dtypes = (x0.dtype, pos_des.dtype, cmd.dtype, foot_lever.dtype)
+        ctx.save_for_backward(x0, pos_des, cmd, t_now, gait, hip)
+        ctx.save_for_forward(x0, pos_des, cmd, t_now, gait, hip)
+        ctx.mark_non_differentiable(contact)
+        ctx.set_materialize_grads(False)    # an output nothing reads arrives as None
+        return xref, contact, r_feet, pos_des_out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_xref, _g_contact, g_r_feet, g_pos_des):
+        want = [n for n, need in zip(_TRAJ, ctx.needs_input_grad[5:]) if need]
+        given = dict(g_xref=g_xref, g_r_feet=g_r_feet, g_pos_des=g_pos_des)
+        grads = [None] * 9
+        if not want or all(g is None for g in given.values()):
+            return tuple(grads)
+        f64 = torch.float64
+        # (Plan.traj_vjp launches on torch's current stream)
+        res = ctx.plan.traj_vjp(*ctx.saved_tensors, ctx.dt, want=want,
+                                **{n: None if g is None else g.to(f64).contiguous()
+                                   for n, g in given.items()})
+        for pos, (n, dtype) in enumerate(zip(_TRAJ, ctx.dtypes)):
+            if n in res:
+                grads[5 + pos] = res[n].to(dtype)
+        return tuple(grads)
+
+    @staticmethod
+    def jvp(ctx, _plan, _dt, _t_now, _gait, _hip, *tangents):
+        given = {n: t.detach().to(dtype).contiguous()
+                 for n, t, dtype in zip(_TRAJ, tangents, ctx.dtypes) if t is not None}
+        if not given:
+            return None, None, None, None
+        # (Plan.traj_jvp launches on torch's current stream)
+        res = ctx.plan.traj_jvp(*ctx.saved_tensors, ctx.dt, given)
+        return res["xref"], None, res["r_feet"], res["pos_des"]
+
+
+def generate_traj(plan, x0, pos_des, cmd, t_now, gait, foot_lever, hip, dt):
+    """:meth:`cmpc.Plan.generate_traj` -> ``(xref, contact, r_feet, pos_des_out)`` with ``xref``,
+    ``r_feet`` and ``pos_des_out`` differentiable in ``x0``, ``pos_des``, ``cmd`` and
+    ``foot_lever``: chained as ``generate_traj -> build_dynamics -> solve``, a loss on the
+    solution is differentiable on the device in the velocity command, and torch sums the paths
+    into ``x0`` (directly into the solve, and through the reference, the footholds and the yaw
+    rotation of the dynamics), which gives the total derivative.
+
+    The forward pass runs on a clone of ``pos_des``: the caller's tensor is not modified, the
+    clamped value is returned as ``pos_des_out`` (feed it to the next tick), and the value before
+    the clamp -- the one the derivative needs -- is what is saved.  ``contact`` is not
+    differentiable.  The backward pass is one :meth:`cmpc.Plan.traj_vjp` launch for exactly the
+    inputs that need a gradient, on the current stream: the incoming gradients are cast to
+    float64 and the float64 results to each input's dtype.  Under forward-mode AD the tangents
+    are one :meth:`cmpc.Plan.traj_jvp` launch for exactly the inputs that carry a tangent.  The
+    contact pattern and the branch of the clamp are held fixed; the derivative is that of the
+    fp64 function on the fp32 inputs, first order only (a second backward raises), and there is
+    none in ``t_now``, ``gait``, ``hip`` or ``dt``.
+
+    Composed with :func:`build_dynamics` and :func:`solve` the gradients pass through fp32 on
+    their way here; the chain that stays in float64 is :meth:`cmpc.Plan.vjp` with
+    ``want=("Ad", "Bd", "xref")`` -> :meth:`cmpc.Plan.dynamics_vjp` -> :meth:`cmpc.Plan.traj_vjp`
+    with ``g_xref``, ``g_r_feet`` and ``g_yaw``."""
+    return _GenerateTraj.apply(plan, dt, t_now, gait, hip, x0, pos_des, cmd, foot_lever)
 
 
 def jvp(plan, Ad, Bd, gd, x0, xref, contact, tangents, mu=None, fz_min=None, Q=None, R=None,

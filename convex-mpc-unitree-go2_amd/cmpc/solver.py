@@ -140,6 +140,22 @@ def _traj_spec(B, N) -> tuple:
 
 
 @_spec
+def _traj_grad_spec(B, N) -> tuple:
+    """(inputs, gradients in, gradients out, tangents in, tangents out) of cmpc_traj_vjp_run and
+    cmpc_traj_jvp_run; the two results are name -> (io field, dtype, shape)."""
+    f32, f64 = torch.float32, torch.float64
+    inputs, outputs = _traj_spec(B, N)
+    moving = {n: inputs[n] for n in _lib.TRAJ_VJP_OUTPUTS}
+    return ({n: s for n, s in inputs.items() if n != "foot_lever"},
+            dict(g_xref=(f64, (B, N, 12)), g_r_feet=(f64, (B, N, 4, 3)), g_yaw=(f64, (B,)),
+                 g_pos_des_out=(f64, (B, 3))),
+            {n: ("g_" + n, f64, shape) for n, (_, shape) in moving.items()},
+            {"d_" + n: s for n, s in moving.items()},
+            dict(xref=("d_xref", *outputs["xref"]), r_feet=("d_r_feet", *outputs["r_feet"]),
+                 pos_des=("d_pos_des_out", f64, (B, 3))))
+
+
+@_spec
 def _leg_spec(B) -> tuple:
     """(inputs, results) of cmpc_leg_torque, ``force`` apart (_force_rows)."""
     f64 = torch.float64
@@ -716,6 +732,87 @@ class Plan:
         return self._pipeline("cmpc_generate_traj", _traj_spec(B, self.params.N),
                               (x0, pos_des, cmd, t_now, gait, foot_lever, hip), out, stream,
                               lambda *p: (B, dt, *p))
+
+    def traj_vjp(self, x0, pos_des, cmd, t_now, gait, hip, dt, g_xref=None, g_r_feet=None,
+                 g_yaw=None, g_pos_des=None, want=None, out=None, stream=None):
+        """Gradients of a loss through :meth:`generate_traj` on the device (cmpc_traj_vjp_run,
+        include/cmpc.h): from dL/dxref, dL/dr_feet, dL/d(mean reference yaw) and the gradient in
+        the desired position it leaves to the gradients in the state, the desired position, the
+        command and the current foot levers.
+
+        ``x0`` .. ``hip`` and ``dt`` as for :meth:`generate_traj`, without ``foot_lever`` (its
+        values are not needed); ``pos_des`` is the value BEFORE :meth:`generate_traj` overwrote it
+        (with the clamped value a clamped robot reads as unclamped) and is not modified.
+        ``g_xref`` (B, N, 12) -- what :meth:`vjp` returns for ``want=("xref",)`` -- ``g_r_feet``
+        (B, N, 4, 3) and ``g_yaw`` (B,) -- what :meth:`dynamics_vjp` returns, ``g_yaw / N`` being
+        added to every step's yaw gradient -- and ``g_pos_des`` (B, 3), the gradient in the
+        desired position after the clamp, are float64 device tensors; each may be None (zeros),
+        one must be given.  ``want`` names the results, a non-empty subset of ``("x0", "pos_des",
+        "cmd", "foot_lever")`` (None: all four); a result does not depend on what else is asked
+        for.  Returns a dict of float64 device tensors of the inputs' shapes; ``x0`` is written
+        whole, zero outside its entries 0, 1, 3, 4, 5.  The contact pattern and the branch of the
+        clamp are held fixed, and the gradient is that of the fp64 function on the fp32 inputs,
+        not of its fp32-rounded outputs.  ``out`` is a dict of preallocated tensors for some or
+        all of the wanted names.  Asynchronous on ``stream`` (default: torch's current stream),
+        no allocation when every wanted name is in ``out``, graph-capturable; B is not limited by
+        max_batch."""
+        self._need("cmpc_traj_vjp_run", "traj_vjp")
+        want = _lib.TRAJ_VJP_OUTPUTS if want is None else tuple(want)
+        if not want or [n for n in want if n not in _lib.TRAJ_VJP_OUTPUTS]:
+            raise ValueError(f"traj_vjp: want {want} must be a non-empty subset of "
+                             f"{_lib.TRAJ_VJP_OUTPUTS}")
+        given = dict(g_xref=g_xref, g_r_feet=g_r_feet, g_yaw=g_yaw, g_pos_des_out=g_pos_des)
+        if all(t is None for t in given.values()):
+            raise ValueError("traj_vjp needs g_xref, g_r_feet, g_yaw or g_pos_des: one must be given")
+        B = x0.shape[0]
+        inputs, grads, results, _, _ = _traj_grad_spec(B, self.params.N)
+        io = _lib.CTrajVjpIO()
+        io.size = ctypes.sizeof(_lib.CTrajVjpIO)
+        self._fill_io(io, inputs, dict(x0=x0, pos_des=pos_des, cmd=cmd, t_now=t_now, gait=gait,
+                                       hip=hip), {})
+        self._fill_io(io, grads, {}, given)
+        res = self._results(io, results, want, (), out, self.device)
+        io.dt = float(dt)
+        self._run_io("cmpc_traj_vjp_run", io, B, stream)
+        return res
+
+    def traj_jvp(self, x0, pos_des, cmd, t_now, gait, hip, dt, tangents,
+                 want=("xref", "r_feet", "pos_des"), out=None, stream=None):
+        """Forward-mode derivative of :meth:`generate_traj` on the device (cmpc_traj_jvp_run,
+        include/cmpc.h): how ``xref``, ``r_feet`` and the desired position it leaves move with
+        the state, the desired position, the command and the current foot levers.
+
+        ``x0`` .. ``hip`` and ``dt`` as for :meth:`traj_vjp` (``pos_des`` before the clamp, not
+        modified).  ``tangents`` is a non-empty dict from input name, one of ``("x0", "pos_des",
+        "cmd", "foot_lever")``, to a device tensor of that input's shape and dtype (fp32,
+        ``pos_des`` float64); an input that is not named does not move.  ``want`` is a non-empty
+        subset of ``("xref", "r_feet", "pos_des")``.  Returns a dict: ``xref`` (B, N, 12) and
+        ``r_feet`` (B, N, 4, 3) fp32, the fp64 derivative rounded once -- what :meth:`jvp` and
+        :meth:`dynamics_jvp` take as those tangents -- and ``pos_des`` (B, 3) float64.  A swing
+        lever's tangent and columns 3, 4, 8, 9, 10 of ``xref``'s are exactly zero.  A result does
+        not depend on what else is asked for.  ``out`` is a dict of preallocated tensors for some
+        or all of the wanted names.  Asynchronous on ``stream`` (default: torch's current
+        stream), no allocation when every wanted name is in ``out``, graph-capturable; B is not
+        limited by max_batch."""
+        self._need("cmpc_traj_jvp_run", "traj_jvp")
+        tangents, want = dict(tangents), tuple(want)
+        if not tangents or [n for n in tangents if n not in _lib.TRAJ_JVP_TANGENTS]:
+            raise ValueError(f"traj_jvp: tangents {tuple(tangents)} must name a non-empty subset "
+                             f"of {_lib.TRAJ_JVP_TANGENTS}")
+        if not want or [n for n in want if n not in _lib.TRAJ_JVP_OUTPUTS]:
+            raise ValueError(f"traj_jvp: want {want} must be a non-empty subset of "
+                             f"{_lib.TRAJ_JVP_OUTPUTS}")
+        B = x0.shape[0]
+        inputs, _, _, moves, results = _traj_grad_spec(B, self.params.N)
+        io = _lib.CTrajJvpIO()
+        io.size = ctypes.sizeof(_lib.CTrajJvpIO)
+        self._fill_io(io, inputs, dict(x0=x0, pos_des=pos_des, cmd=cmd, t_now=t_now, gait=gait,
+                                       hip=hip), {})
+        self._fill_io(io, moves, {"d_" + n: t for n, t in tangents.items()}, {})
+        res = self._results(io, results, want, (), out, self.device)
+        io.dt = float(dt)
+        self._run_io("cmpc_traj_jvp_run", io, B, stream)
+        return res
 
     def leg_torque(self, t, gait, force, J_foot, J_full, M, C, g, dq, Jdot_dq, foot_pos, foot_vel,
                    body, hip, state, tau_max=45.0, out=None, stream=None):

@@ -25,6 +25,7 @@
 #include "cmpc_refine.hip"    // certified float64 refinement around the optimum on the held faces
 #include "cmpc_jvp.hip"       // forward-mode derivatives of the optimum on the held faces
 #include "cmpc_dynamics_grad.hip"  // reverse- and forward-mode derivatives of the dynamics builder
+#include "cmpc_traj_grad.hip"      // reverse- and forward-mode derivatives of the trajectory generator
 
 constexpr int kNumGroups = 3;  // solve kernels (register classes), see solve_group_kernel
 static_assert(kNumGroups == CMPC_NUM_SOLVE_KERNELS, "one timing slot per solve kernel");
@@ -221,6 +222,18 @@ int check_dynamics_grad(const cmpc_plan* pl, int64_t B, float dt, bool inputs, c
   const std::string w(what);
   if (int rc = check_pipeline(pl, what, B < 0)) return rc;
   if (!(dt > 0.f) || !std::isfinite(dt)) return fail(CMPC_E_INVALID, w + ": dt must be > 0");
+  if (B == 0) return CMPC_OK;
+  if (!inputs) return fail(CMPC_E_INVALID, w + ": null array argument");
+  if (missing) return fail(CMPC_E_INVALID, w + missing);
+  return CMPC_OK;
+}
+
+// the same for the two derivative entries of the trajectory generator, whose dt is a double
+int check_traj_grad(const cmpc_plan* pl, int64_t B, double dt, bool inputs, const char* missing,
+                    const char* what) {
+  const std::string w(what);
+  if (int rc = check_pipeline(pl, what, B < 0)) return rc;
+  if (!(dt > 0.0) || !std::isfinite(dt)) return fail(CMPC_E_INVALID, w + ": dt must be > 0");
   if (B == 0) return CMPC_OK;
   if (!inputs) return fail(CMPC_E_INVALID, w + ": null array argument");
   if (missing) return fail(CMPC_E_INVALID, w + missing);
@@ -791,6 +804,52 @@ int cmpc_generate_traj(cmpc_plan* pl, int64_t B, double dt, const float* x0, dou
   const unsigned blocks = grid_stride_blocks((B + cmpc::kTrajGroup - 1) / cmpc::kTrajGroup);
   return launch(cmpc::traj_group_kernel, "traj_group_kernel launch", blocks, 64, 0, stream, pl->kp.N,
                 dt, B, x0, pos_des, cmd, t_now, gait, foot_lever, hip, xref, contact, r_feet);
+}
+
+int cmpc_traj_vjp_run(cmpc_plan* pl, int64_t B, const cmpc_traj_vjp_io* io, void* stream) {
+  const char* what = "cmpc_traj_vjp_run";
+  cmpc_traj_vjp_io a;
+  if (int rc = io_copy(io, offsetof(cmpc_traj_vjp_io, g_x0) + sizeof(io->g_x0), what,
+                       "cmpc_traj_vjp_io", a))
+    return rc;
+  if (int rc = check_traj_grad(
+          pl, B, a.dt, a.x0 && a.pos_des && a.cmd && a.t_now && a.gait && a.hip,
+          !a.g_xref && !a.g_r_feet && !a.g_yaw && !a.g_pos_des_out
+              ? ": every gradient is null (one must be given)"
+          : !a.g_x0 && !a.g_pos_des && !a.g_cmd && !a.g_foot_lever
+              ? ": every output is null (one must be given)"
+              : nullptr,
+          what))
+    return rc;
+  if (B == 0) return CMPC_OK;
+  const cmpc::TrajVjpArgs k{{a.x0, a.pos_des, a.cmd, a.t_now, a.gait, a.hip},
+                            a.g_xref, a.g_r_feet, a.g_yaw, a.g_pos_des_out,
+                            a.g_x0, a.g_pos_des, a.g_cmd, a.g_foot_lever};
+  return launch(cmpc::vjp_traj_kernel, "vjp_traj_kernel launch", grid_stride_blocks(B), 64, 0,
+                stream, pl->kp.N, a.dt, B, k);
+}
+
+int cmpc_traj_jvp_run(cmpc_plan* pl, int64_t B, const cmpc_traj_jvp_io* io, void* stream) {
+  const char* what = "cmpc_traj_jvp_run";
+  cmpc_traj_jvp_io a;
+  if (int rc = io_copy(io, offsetof(cmpc_traj_jvp_io, d_xref) + sizeof(io->d_xref), what,
+                       "cmpc_traj_jvp_io", a))
+    return rc;
+  if (int rc = check_traj_grad(
+          pl, B, a.dt, a.x0 && a.pos_des && a.cmd && a.t_now && a.gait && a.hip,
+          !a.d_x0 && !a.d_pos_des && !a.d_cmd && !a.d_foot_lever
+              ? ": every tangent is null (one must be given)"
+          : !a.d_xref && !a.d_r_feet && !a.d_pos_des_out
+              ? ": every output is null (one must be given)"
+              : nullptr,
+          what))
+    return rc;
+  if (B == 0) return CMPC_OK;
+  const cmpc::TrajJvpArgs k{{a.x0, a.pos_des, a.cmd, a.t_now, a.gait, a.hip},
+                            a.d_x0, a.d_pos_des, a.d_cmd, a.d_foot_lever,
+                            a.d_xref, a.d_r_feet, a.d_pos_des_out};
+  return launch(cmpc::jvp_traj_kernel, "jvp_traj_kernel launch", grid_stride_blocks(B), 64, 0,
+                stream, pl->kp.N, a.dt, B, k);
 }
 
 int cmpc_leg_torque(cmpc_plan* pl, int64_t B, const double* t, const double* gait,

@@ -35,6 +35,31 @@ __device__ __forceinline__ bool stance_at(double t, double period, double duty, 
   return ph < duty;
 }
 
+// The class of the lever of (step k, leg) = (lane >> 2, lane & 3), decided for the whole wave at
+// once (every lane calls): kLeverSwing when the leg is in swing at the step's start (or k >= N),
+// kLeverCurrent when it is in stance and has not taken off at any step <= k, else the last
+// take-off step j <= k, whose predicted touchdown the lever is.  The start-of-step masks and the
+// take-off flags of all (k, leg) are two wave ballots and each lane finds its j with one bit scan.
+// `off` is the lane's leg's phase offset.  Shared with cmpc_traj_grad.hip, whose derivatives hold
+// exactly this pattern fixed.
+constexpr int kLeverSwing = -2, kLeverCurrent = -1;
+__device__ __forceinline__ int lever_class(int lane, int N, double dt, double tn, double period,
+                                           double duty, double off) {
+#pragma clang fp contract(off)
+  const int leg = lane & 3, k = lane >> 2;
+  const bool active = k < N;
+  const bool m = active && stance_at(tn + (double)k * dt, period, duty, off);
+  const uint64_t mbits = __ballot(m);
+  const bool prev_stance = (k == 0) ? true : ((mbits >> (lane - 4)) & 1ull) != 0;
+  const bool to = active && !m && (k == 0 || prev_stance);
+  const uint64_t tbits = __ballot(to);
+  if (!m) return kLeverSwing;
+  const uint64_t legbits = 0x1111111111111111ull << leg;
+  const uint64_t upto = (lane == 63) ? ~0ull : ((2ull << lane) - 1ull);
+  const uint64_t cand = tbits & legbits & upto;
+  return cand == 0 ? kLeverCurrent : (63 - __clzll((long long)cand)) >> 2;
+}
+
 // ---- grouped form: kTrajGroup robots per wave ----
 // The per-robot scalars (clamp, velocities, the three fp64 sin/cos pairs) were computed by all
 // 64 lanes redundantly, and every lane evaluated its own take-off step's sin/cos.  Here a wave
@@ -136,23 +161,15 @@ __global__ void __launch_bounds__(64) traj_group_kernel(int N, double dt, int64_
         t = t + dt / 2;
         contact[b * 4 * N + lane] = stance_at(t, period, duty, u.off[cl]) ? 1 : 0;
       }
-      const bool active = k < N;
-      const bool m = active && stance_at(tn + (double)k * dt, period, duty, u.off[leg]);
-      const uint64_t mbits = __ballot(m);
-      const bool prev_stance = (k == 0) ? true : ((mbits >> (lane - 4)) & 1ull) != 0;
-      const bool to = active && !m && (k == 0 || prev_stance);
-      const uint64_t tbits = __ballot(to);
-      if (active) {
+      const int cls = lever_class(lane, N, dt, tn, period, duty, u.off[leg]);
+      if (k < N) {
         double r0 = 0.0, r1 = 0.0, r2 = 0.0;
-        if (m) {
-          const uint64_t legbits = 0x1111111111111111ull << leg;
-          const uint64_t upto = (lane == 63) ? ~0ull : ((2ull << lane) - 1ull);
-          const uint64_t cand = tbits & legbits & upto;
-          if (cand == 0) {
+        if (cls != kLeverSwing) {
+          if (cls == kLeverCurrent) {
             const float* fl = foot_lever + (b * 4 + leg) * 3;
             r0 = fl[0]; r1 = fl[1]; r2 = fl[2];
           } else {
-            const int j = (63 - __clzll((long long)cand)) >> 2;
+            const int j = cls;
             const double t = (double)(j + 1) * dt;
             const double bx = pdx + vwx * t, by = pdy + vwy * t, bz = pdz + 0.0 * t;
             const double cj = CS[r][j][0], sj = CS[r][j][1];

@@ -694,6 +694,136 @@ int cmpc_generate_traj(cmpc_plan* plan, int64_t B, double dt, const float* x0, d
                        const float* foot_lever, const float* hip, float* xref, uint8_t* contact,
                        float* r_feet, void* stream);
 
+/* Gradients of a loss through cmpc_generate_traj, on the device: from dL/dxref (the fp64 g_xref
+ * cmpc_vjp_run writes), dL/dr_feet and dL/dyaw_avg (the fp64 g_r_feet and g_yaw
+ * cmpc_dynamics_vjp_run writes) and dL/dpos_des' to dL/d(x0, pos_des, cmd, foot_lever).  The
+ * function differentiated is what cmpc_generate_traj evaluates before it rounds, in fp64 on the
+ * fp32 inputs widened exactly.  The contact table and the stance / take-off pattern depend on
+ * t_now and gait alone, are piecewise constant and are held fixed, as is the branch of the clamp:
+ * there is no derivative in t_now, gait, hip or dt.  Per robot, with
+ *   (px, py, phi, theta, psi) = x0[0, 1, 3, 4, 5],   (vxb, vyb, zdes, wz) = cmd,
+ *   t_k = (k + 1) dt,   tau = ((1 - duty) period + 0.5 duty period) / 2,   c, s = cos, sin psi:
+ * clamp:     per axis a of x, y  sigma_a = 1 when cmpc_generate_traj clamps (pos_des[a] - p_a > 0.1
+ *            or p_a - pos_des[a] > 0.1, strict, in that order), else 0;  pd_a = p_a +- 0.1 when
+ *            clamped, else pos_des[a];  pd_z = zdes (pos_des[2] has no effect)
+ * reference: vwx = c vxb - s vyb,  vwy = s vxb + c vyb,
+ *            xref[k] = (pd_x + vwx t_k, pd_y + vwy t_k, pd_z, 0, 0, psi + wz t_k, vwx, vwy, 0, 0,
+ *                       0, wz)
+ * levers:    each (k, leg) is of class S (swing at the step's start: r = 0), C (stance, no
+ *            take-off at a step <= k: r = foot_lever[leg]) or P (stance, last take-off at step
+ *            j <= k), decided as cmpc_generate_traj decides it.  In class P, with
+ *            psi_j = psi + wz t_j, (hwx, hwy) = R_z(psi_j) (hip[leg][0], hip[leg][1]),
+ *            vbx = cos(theta) vxb, vby = sin(theta) sin(phi) vxb + cos(phi) vyb:
+ *              r = (hwx + vbx tau - wz tau hwy,  hwy + vby tau + wz tau hwx,  0.02 - zdes)
+ *            (r does not depend on px, py or pos_des: the base position cancels).
+ * With G = g_xref, plus g_yaw / N on column 5 of every row when g_yaw is given, H = g_r_feet and
+ * gp = g_pos_des_out:
+ *   g_pd_a = sum_k G[k][a] + gp[a]                     g_zdes = sum_k G[k][2] + gp[2] - sum_P H[2]
+ *   g_vwx  = sum_k (t_k G[k][0] + G[k][6])             g_vwy likewise with columns 1 and 7
+ *   g_psi  = sum_k G[k][5]                             g_wz = sum_k (t_k G[k][5] + G[k][11])
+ * over class P:  g_vbx += tau H[0],  g_vby += tau H[1],  g_hwx = H[0] + wz tau H[1],
+ *   g_hwy = H[1] - wz tau H[0],  g_wz += tau (-hwy H[0] + hwx H[1]),
+ *   g_psij = -hwy g_hwx + hwx g_hwy,  g_psi += g_psij,  g_wz += t_j g_psij
+ * over class C:  g_foot_lever[leg] += H[k][leg]
+ * and then
+ *   g_vxb = c g_vwx + s g_vwy + cos(theta) g_vbx + sin(theta) sin(phi) g_vby
+ *   g_vyb = -s g_vwx + c g_vwy + cos(phi) g_vby
+ *   g_psi += -vwy g_vwx + vwx g_vwy
+ *   g_theta = -sin(theta) vxb g_vbx + cos(theta) sin(phi) vxb g_vby
+ *   g_phi = (sin(theta) cos(phi) vxb - sin(phi) vyb) g_vby
+ *   g_x0 = (sigma_x g_pd_x, sigma_y g_pd_y, 0, g_phi, g_theta, g_psi, 0, 0, 0, 0, 0, 0)
+ *   g_pos_des = ((1 - sigma_x) g_pd_x, (1 - sigma_y) g_pd_y, 0)
+ *   g_cmd = (g_vxb, g_vyb, g_zdes, g_wz)
+ *   x0, cmd, t_now, gait, hip   as for cmpc_generate_traj, required
+ *   pos_des       [B][3]  fp64  required, not modified: THE VALUE BEFORE cmpc_generate_traj
+ *                               OVERWROTE IT.  cmpc_generate_traj stores the clamped value in
+ *                               place; with that value a clamped robot reads as unclamped, and
+ *                               its gradient goes to pos_des where it belongs to x0.  Keep a copy.
+ *   dt                          > 0 and finite, else CMPC_E_INVALID
+ *   g_xref        [B][N][12]    fp64, nullable: read as zeros
+ *   g_r_feet      [B][N][4][3]  fp64, nullable: read as zeros
+ *   g_yaw         [B]           fp64, nullable: cmpc_dynamics_vjp_io's g_yaw, added as g_yaw / N
+ *                               to every step's yaw gradient
+ *   g_pos_des_out [B][3]        fp64, nullable: the gradient in the pos_des cmpc_generate_traj
+ *                               leaves behind (a loss that reaches the next tick); all four NULL:
+ *                               CMPC_E_INVALID
+ *   g_x0 [B][12] (written whole), g_pos_des [B][3], g_cmd [B][4], g_foot_lever [B][4][3]   fp64
+ *                               outputs, each nullable, at least one required (else
+ *                               CMPC_E_INVALID).  foot_lever's values are not needed.
+ * An output is bit for bit the same whichever other outputs are asked for.  A NULL gradient and
+ * an array of zeros give equal results (the sign of a zero may differ).  Values are not
+ * validated: a NaN stays in its robot's rows.
+ * `size` is the caller's sizeof of the struct (fields past it read as NULL); it must reach past
+ * `g_x0`.  B >= 0 (B == 0 returns CMPC_OK); no workspace is used, so the plan's max_batch does
+ * not limit B.  Each sum runs in a fixed order: the results are bitwise repeatable and do not
+ * depend on B or on the robot's place in the batch.  Asynchronous on `stream`, no allocation, no
+ * host synchronisation, graph-capturable; the plan's device must be current. */
+typedef struct cmpc_traj_vjp_io {
+  uint32_t size;            /* sizeof of this struct in the caller's header */
+  const float* x0;          /* [B][12] required, as the other inputs */
+  const double* pos_des;    /* [B][3] the value BEFORE cmpc_generate_traj's clamp; not modified */
+  const float* cmd;         /* [B][4] */
+  const double* t_now;      /* [B] */
+  const double* gait;       /* [B][6] */
+  const float* hip;         /* [4][3] */
+  double dt;                /* > 0, finite */
+  const double* g_xref;     /* [B][N][12] nullable: read as zeros, as the next three; one required */
+  const double* g_r_feet;   /* [B][N][4][3] */
+  const double* g_yaw;      /* [B] gradient in the mean reference yaw, spread as g_yaw / N */
+  const double* g_pos_des_out; /* [B][3] gradient in the pos_des cmpc_generate_traj leaves */
+  double* g_x0;             /* [B][12] nullable, as every output; one required */
+  double* g_pos_des;        /* [B][3] */
+  double* g_cmd;            /* [B][4] */
+  double* g_foot_lever;     /* [B][4][3] */
+} cmpc_traj_vjp_io;
+int cmpc_traj_vjp_run(cmpc_plan* plan, int64_t B, const cmpc_traj_vjp_io* io, void* stream);
+
+/* Forward-mode derivative of cmpc_generate_traj, on the device: how xref, r_feet and the pos_des
+ * it leaves move with x0, pos_des, cmd and foot_lever -- cmpc_traj_vjp_io's function and
+ * notation, its Jacobian applied from the other side.  With d_vxb, d_vyb, d_zdes, d_wz = d_cmd
+ * and dp, dphi, dtheta, dpsi from d_x0 (only its entries 0, 1, 3, 4, 5 are read):
+ *   dvwx = c d_vxb - s d_vyb - vwy dpsi,   dvwy = s d_vxb + c d_vyb + vwx dpsi
+ *   dpd_a = sigma_a dp_a + (1 - sigma_a) d_pos_des[a],   dpd_z = d_zdes
+ *   d_xref[k] = (dpd_x + dvwx t_k, dpd_y + dvwy t_k, d_zdes, 0, 0, dpsi + d_wz t_k, dvwx, dvwy,
+ *                0, 0, 0, d_wz)
+ *   dvbx = cos(theta) d_vxb - sin(theta) vxb dtheta
+ *   dvby = (cos(theta) sin(phi) dtheta + sin(theta) cos(phi) dphi) vxb + sin(theta) sin(phi) d_vxb
+ *          - sin(phi) vyb dphi + cos(phi) d_vyb
+ *   class P, with dpsi_j = dpsi + d_wz t_j, dhwx = -hwy dpsi_j, dhwy = hwx dpsi_j:
+ *     d_r = (dhwx + tau dvbx - tau (d_wz hwy + wz dhwy),
+ *            dhwy + tau dvby + tau (d_wz hwx + wz dhwx),  -d_zdes)
+ *   class C: d_r = d_foot_lever[leg];   class S: exactly 0
+ *   d_pos_des_out = (dpd_x, dpd_y, d_zdes)
+ *   x0, pos_des (before the clamp), cmd, t_now, gait, hip, dt   as in cmpc_traj_vjp_io
+ *   d_x0 [B][12] fp32, d_pos_des [B][3] fp64, d_cmd [B][4] fp32, d_foot_lever [B][4][3] fp32
+ *                               each nullable (an input that does not move), at least one required
+ *   d_xref        [B][N][12]    fp32 nullable output; columns 3, 4, 8, 9, 10 are exactly 0
+ *   d_r_feet      [B][N][4][3]  fp32 nullable output
+ *   d_pos_des_out [B][3]        fp64 nullable output; all three NULL: CMPC_E_INVALID
+ * The two fp32 outputs are computed in fp64 and rounded once: they are what cmpc_jvp_io's d_xref
+ * and cmpc_dynamics_jvp_io's d_r_feet and d_xref take.  An output is bit for bit the same
+ * whichever others are asked for; a NULL tangent and an array of zeros give equal results (the
+ * sign of a zero may differ).  Values are treated as in cmpc_traj_vjp_io.  `size` must reach past
+ * `d_xref`; B, the stream, allocation and capture guarantees are cmpc_traj_vjp_run's. */
+typedef struct cmpc_traj_jvp_io {
+  uint32_t size;            /* sizeof of this struct in the caller's header */
+  const float* x0;          /* [B][12] required, as the other inputs */
+  const double* pos_des;    /* [B][3] the value BEFORE cmpc_generate_traj's clamp; not modified */
+  const float* cmd;         /* [B][4] */
+  const double* t_now;      /* [B] */
+  const double* gait;       /* [B][6] */
+  const float* hip;         /* [4][3] */
+  double dt;                /* > 0, finite */
+  const float* d_x0;        /* [B][12] nullable, as the next three; one required */
+  const double* d_pos_des;  /* [B][3] */
+  const float* d_cmd;       /* [B][4] */
+  const float* d_foot_lever; /* [B][4][3] */
+  float* d_xref;            /* [B][N][12] nullable, as every output; one required */
+  float* d_r_feet;          /* [B][N][4][3] */
+  double* d_pos_des_out;    /* [B][3] */
+} cmpc_traj_jvp_io;
+int cmpc_traj_jvp_run(cmpc_plan* plan, int64_t B, const cmpc_traj_jvp_io* io, void* stream);
+
 /* The reference's 1 kHz leg controller for B robots (the consumer of the
  * QP's first forces): LegController.compute_leg_torque for legs FL FR RL RR
  * (leg_controller.py:43-112; test_MPC.py:199-225) -- stance tau = J_foot' (-f) (:100-101),
