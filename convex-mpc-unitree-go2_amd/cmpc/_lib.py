@@ -149,6 +149,38 @@ TRAJ_VJP_OUTPUTS = ("x0", "pos_des", "cmd", "foot_lever")
 TRAJ_JVP_TANGENTS = ("x0", "pos_des", "cmd", "foot_lever")
 TRAJ_JVP_OUTPUTS = ("xref", "r_feet", "pos_des")
 
+def _srb_io_fields(*names):
+    """``size``, cmpc_srb_step's arguments (``force_stride``, ``nsub`` and ``dt`` by value), then
+    the named fields."""
+    values = dict(force_stride=ctypes.c_int64, nsub=ctypes.c_int32, dt=ctypes.c_double)
+    head = ("t_now", "gait", "mass", "inertia_body", "force", "force_stride", "hip", "x", "feet",
+            "contact_state", "nsub", "dt")
+    return ([("size", ctypes.c_uint32)] +
+            [(n, values.get(n, ctypes.c_void_p)) for n in head + names])
+
+
+class CSrbVjpIO(ctypes.Structure):
+    """cmpc_srb_vjp_io (include/cmpc.h): a batch of robots whose gradients through the rigid-body
+    plant are wanted, given dL/dx' and dL/dfeet'.  ``size`` is this mirror's sizeof."""
+    _fields_ = _srb_io_fields("g_x_out", "g_feet_out", "g_x", "g_feet", "g_force", "g_mass",
+                              "g_inertia_body")
+
+
+class CSrbJvpIO(ctypes.Structure):
+    """cmpc_srb_jvp_io (include/cmpc.h): a batch of robots whose forward-mode derivative of the
+    rigid-body plant is wanted, given the tangents of its inputs.  ``size`` is this mirror's
+    sizeof."""
+    _fields_ = _srb_io_fields("d_x", "d_feet", "d_force", "d_mass", "d_inertia_body", "d_x_out",
+                              "d_feet_out")
+
+
+# Plan.srb_vjp's results (field g_<name> of cmpc_srb_vjp_io)
+SRB_VJP_OUTPUTS = ("x", "feet", "force", "mass", "inertia_body")
+# Plan.srb_jvp's tangents (field d_<name> of cmpc_srb_jvp_io) and results (field d_<name>_out)
+SRB_JVP_TANGENTS = SRB_VJP_OUTPUTS
+SRB_JVP_OUTPUTS = ("x", "feet")
+SRB_GRAD_MAX_NSUB = 64  # CMPC_SRB_GRAD_MAX_NSUB
+
 # cmpc_refine_io's info values below zero (CMPC_REFINE_*) and the results Plan.refine can return
 REFINE_INVALID, REFINE_ROUNDS, REFINE_CYCLE, REFINE_MAX_ROUNDS = -1, -2, -3, 16
 REFINE_OUTPUTS = ("info", "res", "w64", "lam", "faces")
@@ -205,7 +237,8 @@ def _prototypes() -> dict:
                      ("cmpc_refine_run", CRefineIO), ("cmpc_jvp_run", CJvpIO),
                      ("cmpc_dynamics_vjp_run", CDynamicsVjpIO),
                      ("cmpc_dynamics_jvp_run", CDynamicsJvpIO),
-                     ("cmpc_traj_vjp_run", CTrajVjpIO), ("cmpc_traj_jvp_run", CTrajJvpIO)):
+                     ("cmpc_traj_vjp_run", CTrajVjpIO), ("cmpc_traj_jvp_run", CTrajJvpIO),
+                     ("cmpc_srb_vjp_run", CSrbVjpIO), ("cmpc_srb_jvp_run", CSrbJvpIO)):
         table[name] = ([vp, i64, ptr(io), vp], rc)
     return table
 

@@ -18,6 +18,21 @@ the current foot levers (one :meth:`cmpc.Plan.traj_vjp` or :meth:`cmpc.Plan.traj
 DESIGN.md 4u): chained into ``build_dynamics`` and ``solve``, a loss on the solution reaches the
 command, and the gradient in ``x0`` is the total one.
 
+``srb_step(plan, ...)`` is :meth:`cmpc.Plan.srb_step` as a function: it steps clones and its
+advanced state and feet carry a gradient in the state, the feet, the held forces, the mass and the
+body inertia (one :meth:`cmpc.Plan.srb_vjp` or :meth:`cmpc.Plan.srb_jvp` launch).
+``tick(plan, state, ...)`` chains the four layers into the closed loop's tick, and composing it K
+times is a K-tick rollout: a loss on where the robot is after K ticks is differentiable in every
+tick's command, in the initial state, and in mass and inertia (backpropagation through time), and
+forward mode gives the sensitivity of the rollout.
+
+What the gradient of a rollout sees and does not see: the face set of each tick's QP is held
+(below), and so is the branch of the desired-position clamp; the contact schedule of the plant and
+of the trajectory generator depends on time and gait alone, so it is exact, not held; and between
+the layers the values and their gradients pass through fp32 (the dtype of ``w``, ``Ad``, ``Bd``,
+``xref``, ``x``), each layer's own derivative being that of its fp64 function on those fp32
+values.  A warm start does not enter: the function is the optimum on the held faces.
+
 The gradient is that of the fp64 optimum on the faces of the friction pyramid the returned
 ``w`` holds, with that face set fixed -- the function :meth:`cmpc.Plan.gain` solves -- not of the
 fp32 ``w`` itself: the two differ by the solver's tolerance, and where ``w`` sits within
@@ -238,6 +253,112 @@ def generate_traj(plan, x0, pos_des, cmd, t_now, gait, foot_lever, hip, dt):
     ``want=("Ad", "Bd", "xref")`` -> :meth:`cmpc.Plan.dynamics_vjp` -> :meth:`cmpc.Plan.traj_vjp`
     with ``g_xref``, ``g_r_feet`` and ``g_yaw``."""
     return _GenerateTraj.apply(plan, dt, t_now, gait, hip, x0, pos_des, cmd, foot_lever)
+
+
+_SRB = ("x", "feet", "force", "mass", "inertia_body")  # positions 7..11 of _SrbStep's inputs
+
+
+class _SrbStep(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, nsub, dt, t_now, gait, hip, contact_state, x, feet, force, mass,
+                inertia_body):
+        x_out, feet_out, contact_out = x.clone(), feet.clone(), contact_state.clone()
+        plan.srb_step(t_now, gait, mass, inertia_body, force, hip, x_out, feet_out, contact_out,
+                      nsub, dt)
+        ctx.plan, ctx.nsub, ctx.dt = plan, nsub, dt
+        ctx.dtypes = (x.dtype, feet.dtype, force.dtype, mass.dtype, inertia_body.dtype)
+        ctx.force_shape = tuple(force.shape)
+        saved = (t_now, gait, mass, inertia_body, force, hip, x, feet, contact_state)
+        ctx.save_for_backward(*saved)       # x, feet, contact_state: the values before the step
+        ctx.save_for_forward(*saved)
+        ctx.mark_non_differentiable(contact_out)
+        ctx.set_materialize_grads(False)    # an output nothing reads arrives as None
+        return x_out, feet_out, contact_out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_x, g_feet, _g_contact):
+        want = [n for n, need in zip(_SRB, ctx.needs_input_grad[7:]) if need]
+        grads = [None] * 12
+        if not want or (g_x is None and g_feet is None):
+            return tuple(grads)
+        f64 = torch.float64
+        # (Plan.srb_vjp launches on torch's current stream)
+        res = ctx.plan.srb_vjp(*ctx.saved_tensors, ctx.nsub, ctx.dt,
+                               g_x=None if g_x is None else g_x.to(f64).contiguous(),
+                               g_feet=None if g_feet is None else g_feet.to(f64).contiguous(),
+                               want=want)
+        for pos, (n, dtype) in enumerate(zip(_SRB, ctx.dtypes)):
+            if n in res:
+                g = res[n].to(dtype)
+                if n == "force" and ctx.force_shape[1] > 12:   # rows wider than U[:, 0]
+                    wide = g.new_zeros(ctx.force_shape)
+                    wide[:, :12] = g
+                    g = wide
+                grads[7 + pos] = g
+        return tuple(grads)
+
+    @staticmethod
+    def jvp(ctx, _plan, _nsub, _dt, _t_now, _gait, _hip, _contact, *tangents):
+        given = {n: t.detach().to(torch.float32) for n, t in zip(_SRB, tangents) if t is not None}
+        if not given:
+            return None, None, None
+        if "force" in given:
+            given["force"] = given["force"][:, :12]
+        given = {n: t.contiguous() for n, t in given.items()}
+        # (Plan.srb_jvp launches on torch's current stream)
+        res = ctx.plan.srb_jvp(*ctx.saved_tensors, ctx.nsub, ctx.dt, given)
+        return res["x"], res["feet"], None
+
+
+def srb_step(plan, t_now, gait, mass, inertia_body, force, hip, x, feet, contact_state, nsub, dt):
+    """:meth:`cmpc.Plan.srb_step` as a function -> ``(x', feet', contact')``: the caller's ``x``,
+    ``feet`` and ``contact_state`` are not modified, the step runs on clones, and ``x'`` and
+    ``feet'`` are differentiable in ``x``, ``feet``, ``force``, ``mass`` and ``inertia_body``;
+    ``contact'`` is not differentiable.  ``force`` is (B, 12) fp32 or a view of such rows, e.g.
+    ``w[:, 12 N:12 N + 12]`` of a solve, which carries the gradient on into :func:`solve`.
+
+    The backward pass is one :meth:`cmpc.Plan.srb_vjp` launch for exactly the inputs that need a
+    gradient, on the current stream, with the saved values from before the step: the incoming
+    gradients are cast to float64 and the float64 results to each input's dtype.  Under
+    forward-mode AD the tangents are one :meth:`cmpc.Plan.srb_jvp` launch for exactly the inputs
+    that carry a tangent.  The contact schedule depends on ``t_now``, ``gait`` and
+    ``contact_state`` alone, so the derivative is exact: that of the documented model in fp64 on
+    the fp32 inputs (not of the step's fp32 arithmetic), first order only (a second backward
+    raises), and there is none in ``t_now``, ``gait``, ``hip`` or ``dt``.  ``nsub`` is at most 64."""
+    return _SrbStep.apply(plan, nsub, dt, t_now, gait, hip, contact_state, x, feet, force, mass,
+                          inertia_body)
+
+
+def tick(plan, state, cmd, gait, hip, mass, inertia_body, dt, nsub, mu=None, fz_min=None, Q=None,
+         R=None):
+    """One tick of :class:`cmpc.closed_loop.ClosedLoop` as a differentiable function ->
+    ``(state', w, status)``.  ``state`` is a dict of ``x`` (B, 12) fp32, ``feet`` (B, 4, 3) fp32,
+    ``contact_state`` (B,) uint8, ``pos_des`` (B, 3) float64 and ``t`` (B,) float64; none of its
+    tensors is modified and ``state'`` holds new ones, so composing ``tick`` K times is the
+    K-tick rollout.  The tick: levers ``feet - p`` and ``I_world = R I_body R'`` by torch ops,
+    :func:`generate_traj` -> :func:`build_dynamics` -> :func:`solve` (cold: a warm start does not
+    enter the derivative) -> :func:`srb_step` of ``nsub`` substeps of ``dt / nsub`` under
+    ``w[:, 12 N:12 N + 12]``, and ``t + dt``.  ``state'["x"]``, ``["feet"]`` and ``["pos_des"]``
+    and ``w`` are differentiable in ``state["x"]``, ``["feet"]``, ``["pos_des"]``, ``cmd``,
+    ``mass``, ``inertia_body`` and the per-robot ``mu``, ``fz_min``, ``Q``, ``R``; see the
+    module's note on what such a gradient sees."""
+    from .closed_loop import rot_zyx
+    N = plan.params.N
+    x, feet, t = state["x"], state["feet"], state["t"]
+    lever = feet - x[:, None, 0:3]
+    Rm = rot_zyx(x[:, 3:6])
+    RI = (Rm[:, :, :, None] * inertia_body[:, None, :, :]).sum(2)
+    I_world = (RI[:, :, None, :] * Rm[:, None, :, :]).sum(3)
+    xref, contact, r_feet, pos_des = generate_traj(plan, x, state["pos_des"], cmd, t, gait, lever,
+                                                   hip, dt)
+    Ad, Bd, gd = build_dynamics(plan, mass, I_world, r_feet, xref, dt)
+    w, status, _ = solve(plan, Ad, Bd, gd, x, xref, contact, mu=mu, fz_min=fz_min, Q=Q, R=R)
+    x_out, feet_out, contact_out = srb_step(plan, t, gait, mass, inertia_body,
+                                            w[:, 12 * N:12 * N + 12], hip, x, feet,
+                                            state["contact_state"], nsub, dt / nsub)
+    return (dict(x=x_out, feet=feet_out, contact_state=contact_out, pos_des=pos_des, t=t + dt),
+            w, status)
 
 
 def jvp(plan, Ad, Bd, gd, x0, xref, contact, tangents, mu=None, fz_min=None, Q=None, R=None,

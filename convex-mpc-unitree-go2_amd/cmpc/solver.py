@@ -176,6 +176,21 @@ def _srb_spec(B) -> tuple:
                  feet=(f32, (B, 4, 3)), contact_state=(torch.uint8, (B,))), {})
 
 
+@_spec
+def _srb_grad_spec(B) -> tuple:
+    """(inputs, gradients in, gradients out, tangents in, tangents out) of cmpc_srb_vjp_run and
+    cmpc_srb_jvp_run, ``force`` apart (_force_rows); the two results are name -> (io field, dtype,
+    shape).  ``force``'s gradient and tangent are packed (B, 12)."""
+    f32, f64 = torch.float32, torch.float64
+    inputs, _ = _srb_spec(B)
+    moving = dict(x=(B, 12), feet=(B, 4, 3), force=(B, 12), mass=(B,), inertia_body=(B, 3, 3))
+    return (inputs,
+            dict(g_x_out=(f64, (B, 12)), g_feet_out=(f64, (B, 4, 3))),
+            {n: ("g_" + n, f64, moving[n]) for n in _lib.SRB_VJP_OUTPUTS},
+            {"d_" + n: (f32, moving[n]) for n in _lib.SRB_JVP_TANGENTS},
+            {n: ("d_" + n + "_out", f32, moving[n]) for n in _lib.SRB_JVP_OUTPUTS})
+
+
 def _problem(Ad, Bd, gd, x0, xref, contact, **more) -> dict:
     """name -> tensor of the six problem arrays and what else an entry requires."""
     return dict(Ad=Ad, Bd=Bd, gd=gd, x0=x0, xref=xref, contact=contact, **more)
@@ -843,6 +858,88 @@ class Plan:
             (t_now, gait, mass, inertia_body, hip, x, feet, contact_state), None, stream,
             lambda t_, gait_, mass_, inertia_, *p: (B, int(nsub), dt, t_, gait_, mass_, inertia_,
                                                     force.data_ptr(), force.stride(0), *p))
+
+    def _srb_grad_io(self, io, inputs, t_now, gait, mass, inertia_body, force, hip, x, feet,
+                     contact_state, nsub, dt):
+        """The part of cmpc_srb_vjp_io and cmpc_srb_jvp_io that is cmpc_srb_step's arguments."""
+        B = x.shape[0]
+        _force_rows(force, B, self.device)
+        io.size = ctypes.sizeof(type(io))
+        self._fill_io(io, inputs, dict(t_now=t_now, gait=gait, mass=mass, inertia_body=inertia_body,
+                                       hip=hip, x=x, feet=feet, contact_state=contact_state), {})
+        io.force, io.force_stride = force.data_ptr(), force.stride(0)
+        io.nsub, io.dt = int(nsub), float(dt)
+
+    def srb_vjp(self, t_now, gait, mass, inertia_body, force, hip, x, feet, contact_state, nsub, dt,
+                g_x=None, g_feet=None, want=None, out=None, stream=None):
+        """Gradients of a loss through :meth:`srb_step` on the device (cmpc_srb_vjp_run,
+        include/cmpc.h): from dL/dx' and dL/dfeet' to the gradients in the state, the feet, the
+        held forces, the mass and the body inertia.
+
+        ``t_now`` .. ``dt`` as for :meth:`srb_step`, but ``x``, ``feet`` and ``contact_state`` are
+        the values BEFORE :meth:`srb_step` advanced them (keep a copy) and are not modified;
+        ``nsub`` is in 1 .. 64.  ``g_x`` (B, 12) and ``g_feet`` (B, 4, 3) are float64 device
+        tensors, the gradients in the advanced state and feet; each may be None (zeros), one must
+        be given.  ``want`` names the results, a non-empty subset of ``("x", "feet", "force",
+        "mass", "inertia_body")`` (None: all five); a result does not depend on what else is asked
+        for.  Returns a dict of float64 device tensors of the inputs' shapes (``force``: packed
+        (B, 12)).  The contact schedule depends on ``t_now``, ``gait`` and ``contact_state``
+        alone, so the gradient is exact, that of the fp64 model on the fp32 inputs; there is none
+        in ``t_now``, ``gait``, ``hip`` or ``dt``.  ``out`` is a dict of preallocated tensors for
+        some or all of the wanted names.  Asynchronous on ``stream`` (default: torch's current
+        stream), no allocation when every wanted name is in ``out``, graph-capturable; B is not
+        limited by max_batch."""
+        self._need("cmpc_srb_vjp_run", "srb_vjp")
+        want = _lib.SRB_VJP_OUTPUTS if want is None else tuple(want)
+        if not want or [n for n in want if n not in _lib.SRB_VJP_OUTPUTS]:
+            raise ValueError(f"srb_vjp: want {want} must be a non-empty subset of "
+                             f"{_lib.SRB_VJP_OUTPUTS}")
+        given = dict(g_x_out=g_x, g_feet_out=g_feet)
+        if all(t is None for t in given.values()):
+            raise ValueError("srb_vjp needs g_x or g_feet: one must be given")
+        B = x.shape[0]
+        inputs, grads, results, _, _ = _srb_grad_spec(B)
+        io = _lib.CSrbVjpIO()
+        self._srb_grad_io(io, inputs, t_now, gait, mass, inertia_body, force, hip, x, feet,
+                          contact_state, nsub, dt)
+        self._fill_io(io, grads, {}, given)
+        res = self._results(io, results, want, (), out, self.device)
+        self._run_io("cmpc_srb_vjp_run", io, B, stream)
+        return res
+
+    def srb_jvp(self, t_now, gait, mass, inertia_body, force, hip, x, feet, contact_state, nsub, dt,
+                tangents, want=("x", "feet"), out=None, stream=None):
+        """Forward-mode derivative of :meth:`srb_step` on the device (cmpc_srb_jvp_run,
+        include/cmpc.h): how the advanced state and feet move with the state, the feet, the held
+        forces, the mass and the body inertia.
+
+        ``t_now`` .. ``dt`` as for :meth:`srb_vjp` (``x``, ``feet`` and ``contact_state`` before
+        the step, not modified).  ``tangents`` is a non-empty dict from input name, one of ``("x",
+        "feet", "force", "mass", "inertia_body")``, to an fp32 device tensor of that input's shape
+        (``force``: packed (B, 12)); an input that is not named does not move.  ``want`` is a
+        non-empty subset of ``("x", "feet")``.  Returns a dict of fp32 tensors, the fp64
+        derivative rounded once -- what :meth:`jvp` and :meth:`traj_jvp` take as the tangent of
+        ``x0``.  A result does not depend on what else is asked for.  ``out`` is a dict of
+        preallocated tensors for some or all of the wanted names.  Asynchronous on ``stream``
+        (default: torch's current stream), no allocation when every wanted name is in ``out``,
+        graph-capturable; B is not limited by max_batch."""
+        self._need("cmpc_srb_jvp_run", "srb_jvp")
+        tangents, want = dict(tangents), tuple(want)
+        if not tangents or [n for n in tangents if n not in _lib.SRB_JVP_TANGENTS]:
+            raise ValueError(f"srb_jvp: tangents {tuple(tangents)} must name a non-empty subset "
+                             f"of {_lib.SRB_JVP_TANGENTS}")
+        if not want or [n for n in want if n not in _lib.SRB_JVP_OUTPUTS]:
+            raise ValueError(f"srb_jvp: want {want} must be a non-empty subset of "
+                             f"{_lib.SRB_JVP_OUTPUTS}")
+        B = x.shape[0]
+        inputs, _, _, moves, results = _srb_grad_spec(B)
+        io = _lib.CSrbJvpIO()
+        self._srb_grad_io(io, inputs, t_now, gait, mass, inertia_body, force, hip, x, feet,
+                          contact_state, nsub, dt)
+        self._fill_io(io, moves, {"d_" + n: t for n, t in tangents.items()}, {})
+        res = self._results(io, results, want, (), out, self.device)
+        self._run_io("cmpc_srb_jvp_run", io, B, stream)
+        return res
 
 
 def leg_state(B: int, device="cuda") -> torch.Tensor:

@@ -26,6 +26,7 @@
 #include "cmpc_jvp.hip"       // forward-mode derivatives of the optimum on the held faces
 #include "cmpc_dynamics_grad.hip"  // reverse- and forward-mode derivatives of the dynamics builder
 #include "cmpc_traj_grad.hip"      // reverse- and forward-mode derivatives of the trajectory generator
+#include "cmpc_sim_grad.hip"       // reverse- and forward-mode derivatives of the rigid-body plant
 
 constexpr int kNumGroups = 3;  // solve kernels (register classes), see solve_group_kernel
 static_assert(kNumGroups == CMPC_NUM_SOLVE_KERNELS, "one timing slot per solve kernel");
@@ -238,6 +239,31 @@ int check_traj_grad(const cmpc_plan* pl, int64_t B, double dt, bool inputs, cons
   if (!inputs) return fail(CMPC_E_INVALID, w + ": null array argument");
   if (missing) return fail(CMPC_E_INVALID, w + missing);
   return CMPC_OK;
+}
+
+// the same for the two derivative entries of the plant: cmpc_srb_step's checks, with nsub in
+// 1 .. CMPC_SRB_GRAD_MAX_NSUB
+template <class IO>
+int check_srb_grad(const cmpc_plan* pl, int64_t B, const IO& a, const char* missing,
+                   const char* what) {
+  const std::string w(what);
+  if (int rc = check_pipeline(pl, what, B < 0)) return rc;
+  if (a.nsub < 1 || a.nsub > CMPC_SRB_GRAD_MAX_NSUB)
+    return fail(CMPC_E_INVALID, w + ": nsub must be in 1 .. " + std::to_string(CMPC_SRB_GRAD_MAX_NSUB));
+  if (!(a.dt > 0.0) || !std::isfinite(a.dt)) return fail(CMPC_E_INVALID, w + ": dt must be > 0");
+  if (a.force_stride < 12) return fail(CMPC_E_INVALID, w + ": force_stride must be >= 12");
+  if (B == 0) return CMPC_OK;
+  if (!a.t_now || !a.gait || !a.mass || !a.inertia_body || !a.force || !a.hip || !a.x || !a.feet ||
+      !a.contact_state)
+    return fail(CMPC_E_INVALID, w + ": null array argument");
+  if (missing) return fail(CMPC_E_INVALID, w + missing);
+  return CMPC_OK;
+}
+
+template <class IO>
+cmpc::SrbIn srb_in(const IO& a) {
+  return {a.t_now, a.gait, a.mass, a.inertia_body, a.force, a.force_stride, a.hip, a.x, a.feet,
+          a.contact_state};
 }
 
 }  // namespace
@@ -886,6 +912,51 @@ int cmpc_srb_step(cmpc_plan* pl, int64_t B, int nsub, double dt, const double* t
   const unsigned blocks = (unsigned)((B + 255) / 256);
   return launch(cmpc::srb_kernel, "srb_kernel launch", blocks, 256, 0, stream, B, nsub, dt, t_now,
                 gait, mass, inertia_body, force, force_stride, hip, x, feet, contact_state);
+}
+
+int cmpc_srb_vjp_run(cmpc_plan* pl, int64_t B, const cmpc_srb_vjp_io* io, void* stream) {
+  const char* what = "cmpc_srb_vjp_run";
+  cmpc_srb_vjp_io a;
+  if (int rc = io_copy(io, offsetof(cmpc_srb_vjp_io, g_x) + sizeof(io->g_x), what,
+                       "cmpc_srb_vjp_io", a))
+    return rc;
+  if (int rc = check_srb_grad(
+          pl, B, a,
+          !a.g_x_out && !a.g_feet_out ? ": every gradient is null (one must be given)"
+          : !a.g_x && !a.g_feet && !a.g_force && !a.g_mass && !a.g_inertia_body
+              ? ": every output is null (one must be given)"
+              : nullptr,
+          what))
+    return rc;
+  if (B == 0) return CMPC_OK;
+  const cmpc::SrbVjpArgs k{srb_in(a), a.g_x_out, a.g_feet_out,
+                           a.g_x, a.g_feet, a.g_force, a.g_mass, a.g_inertia_body};
+  // one thread per robot, one wave per block; a short call's tape leaves room for two blocks per CU
+  const auto kernel = a.nsub <= cmpc::kSrbShortNsub ? cmpc::srb_vjp_kernel<cmpc::kSrbStoredShort>
+                                                    : cmpc::srb_vjp_kernel<cmpc::kSrbStoredMax>;
+  return launch(kernel, "srb_vjp_kernel launch", (unsigned)((B + 63) / 64), 64, 0, stream, B,
+                (int)a.nsub, a.dt, k);
+}
+
+int cmpc_srb_jvp_run(cmpc_plan* pl, int64_t B, const cmpc_srb_jvp_io* io, void* stream) {
+  const char* what = "cmpc_srb_jvp_run";
+  cmpc_srb_jvp_io a;
+  if (int rc = io_copy(io, offsetof(cmpc_srb_jvp_io, d_x_out) + sizeof(io->d_x_out), what,
+                       "cmpc_srb_jvp_io", a))
+    return rc;
+  if (int rc = check_srb_grad(
+          pl, B, a,
+          !a.d_x && !a.d_feet && !a.d_force && !a.d_mass && !a.d_inertia_body
+              ? ": every tangent is null (one must be given)"
+          : !a.d_x_out && !a.d_feet_out ? ": every output is null (one must be given)"
+                                        : nullptr,
+          what))
+    return rc;
+  if (B == 0) return CMPC_OK;
+  const cmpc::SrbJvpArgs k{srb_in(a), a.d_x, a.d_feet, a.d_force, a.d_mass, a.d_inertia_body,
+                           a.d_x_out, a.d_feet_out};
+  return launch(cmpc::srb_jvp_kernel, "srb_jvp_kernel launch", (unsigned)((B + 63) / 64), 64, 0,
+                stream, B, (int)a.nsub, a.dt, k);
 }
 
 int cmpc_plan_set_timing(cmpc_plan* pl, int enable) {

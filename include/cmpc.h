@@ -865,6 +865,125 @@ int cmpc_srb_step(cmpc_plan* plan, int64_t B, int nsub, double dt, const double*
                   const float* force, int64_t force_stride, const float* hip, float* x,
                   float* feet, uint8_t* contact_state, void* stream);
 
+/* Gradients of a loss through cmpc_srb_step, on the device: from dL/dx' and dL/dfeet' to the
+ * gradients in the state, the feet, the held forces, the mass and the body inertia.  The function
+ * differentiated is the plant's documented model evaluated in fp64 on the fp32
+ * inputs widened exactly -- not srb_kernel's fp32 arithmetic.  Per robot, with the state
+ * (p, e = rpy, v, w), the feet c_l, ts = duty period (fp64), g = (0, 0, -9.81) and h = dt; t starts
+ * at t_now and advances by repeated addition of h.  One substep:
+ *   1. sigma_l = stance_at(t, period, duty, offset_l).  A leg with sigma_l set that was not in
+ *      stance before (before the first substep: contact_state) lands:
+ *        c_l = (p_x + cy hx - sy hy + v_x ts / 2,  p_y + sy hx + cy hy + v_y ts / 2,  0)
+ *      with (hx, hy) = hip[l] and the substep's starting p, yaw and v.
+ *   2. R = Rz Ry Rx (e), Iw = R Ib R', F = sum sigma f_l, T = sum sigma (c_l - p) x f_l,
+ *      y = Iw w, alpha = Iw^-1 (T - w x y): a general 3 x 3 inverse, all 9 entries of Ib
+ *      independent, no symmetrisation (as in cmpc_dynamics_vjp_io).
+ *   3. v' = v + h (F / m + g),  w' = w + h alpha,  p' = p + h v',  e' = e + h E(e) w', E the ZYX
+ *      rate map at the substep's starting e:
+ *        roll' = (cy wx + sy wy) / cp,  pitch' = -sy wx + cy wy,  yaw' = wz + sp roll'.
+ * The stance pattern and the landings depend on t_now, gait and contact_state alone, so they are
+ * piecewise constant: there is no derivative in t_now, gait, hip or dt, and the derivative in
+ * everything else is exact, not a held-branch approximation.  The tangent of a substep:
+ *   dR = sum_i dR/de_i de_i,   dIw = dR Ib R' + R dIb R' + R Ib dR'
+ *   dT = sum sigma [(dc_l - dp) x f_l + (c_l - p) x df_l]
+ *   dalpha = Iw^-1 (dT - dw x y - w x (dIw w + Iw dw) - dIw alpha)
+ *   dv' = dv + h (sum sigma df_l / m - F dm / m^2),  dw' = dw + h dalpha,  dp' = dp + h dv'
+ *   de' = de + h (dE[de] w' + E dw')
+ *   at a landing: dc_l = (dp_x - (sy hx + cy hy) dpsi + dv_x ts / 2,
+ *                         dp_y + (cy hx - sy hy) dpsi + dv_y ts / 2,  0),
+ *   which replaces the leg's previous tangent; a foot that does not land keeps dc_l.
+ * The reverse pass is the transpose of that, applied from the last substep to the first; within a
+ * substep the landing comes after the dynamics: the leg's foot adjoint flows into p_x, p_y, psi,
+ * v_x, v_y of the substep's start and is then zero.
+ *   t_now, gait, mass, inertia_body, hip, nsub, dt   as for cmpc_srb_step, required
+ *   force, force_stride (>= 12)   as for cmpc_srb_step (w_out + 12 N with stride 24 N works)
+ *   x [B][12] fp32, feet [B][4][3] fp32, contact_state [B] uint8   required, not modified: THE
+ *                               VALUES BEFORE cmpc_srb_step OVERWROTE THEM.  cmpc_srb_step
+ *                               advances all three in place; with the advanced values the
+ *                               derivative is that of the next tick.  Keep a copy.
+ *   nsub                        1 .. CMPC_SRB_GRAD_MAX_NSUB, else CMPC_E_INVALID
+ *   dt                          > 0 and finite, else CMPC_E_INVALID
+ *   g_x_out    [B][12]          fp64, nullable: read as zeros
+ *   g_feet_out [B][4][3]        fp64, nullable: read as zeros; both NULL: CMPC_E_INVALID
+ *   g_x [B][12], g_feet [B][4][3], g_force [B][12] (packed), g_mass [B], g_inertia_body [B][3][3]
+ *                               fp64 outputs, each nullable, at least one required (else
+ *                               CMPC_E_INVALID)
+ * An output is bit for bit the same whichever other outputs are asked for.  A NULL gradient and
+ * an array of zeros give equal results (the sign of a zero may differ).  g_force of a leg that is
+ * in swing at every substep is exactly 0; g_feet of a leg that is never in stance before it lands
+ * is exactly 0, and without a landing it is g_feet_out plus the lever terms.  Values are not
+ * validated, as in cmpc_srb_step: a pitch of +-pi/2 or a singular Iw gives the Inf or NaN the
+ * arithmetic gives, in that robot's rows only.
+ * `size` is the caller's sizeof of the struct (fields past it read as NULL); it must reach past
+ * `g_x`.  B >= 0 (B == 0 returns CMPC_OK); no workspace is used, so the plan's max_batch does not
+ * limit B.  Every sum runs in a fixed order: the results are bitwise repeatable and do not depend
+ * on B or on the robot's place in the batch.  Asynchronous on `stream`, no allocation, no host
+ * synchronisation, graph-capturable; the plan's device must be current. */
+#define CMPC_SRB_GRAD_MAX_NSUB 64
+typedef struct cmpc_srb_vjp_io {
+  uint32_t size;               /* sizeof of this struct in the caller's header */
+  const double* t_now;         /* [B] required, as the other inputs */
+  const double* gait;          /* [B][6] */
+  const float* mass;           /* [B] */
+  const float* inertia_body;   /* [B][3][3] */
+  const float* force;          /* rows of 12, row stride force_stride floats */
+  int64_t force_stride;        /* >= 12 */
+  const float* hip;            /* [4][3] */
+  const float* x;              /* [B][12] the value BEFORE cmpc_srb_step; not modified */
+  const float* feet;           /* [B][4][3] likewise */
+  const uint8_t* contact_state; /* [B] likewise */
+  int32_t nsub;                /* 1 .. CMPC_SRB_GRAD_MAX_NSUB */
+  double dt;                   /* > 0, finite */
+  const double* g_x_out;       /* [B][12] nullable: read as zeros, as the next; one required */
+  const double* g_feet_out;    /* [B][4][3] */
+  double* g_x;                 /* [B][12] nullable, as every output; one required */
+  double* g_feet;              /* [B][4][3] */
+  double* g_force;             /* [B][12] packed */
+  double* g_mass;              /* [B] */
+  double* g_inertia_body;      /* [B][3][3] */
+} cmpc_srb_vjp_io;
+int cmpc_srb_vjp_run(cmpc_plan* plan, int64_t B, const cmpc_srb_vjp_io* io, void* stream);
+
+/* Forward-mode derivative of cmpc_srb_step, on the device: how x' and feet' move with x, feet, the
+ * held forces, the mass and the body inertia -- cmpc_srb_vjp_io's function and notation, its
+ * Jacobian applied from the other side, primal and tangent advanced together in fp64.
+ *   t_now .. dt                 as in cmpc_srb_vjp_io: x, feet, contact_state before the step
+ *   d_x [B][12], d_feet [B][4][3], d_force [B][12] (packed), d_mass [B], d_inertia_body [B][3][3]
+ *                               fp32, widened exactly, each nullable (an input that does not
+ *                               move), at least one required
+ *   d_x_out    [B][12]          fp32 nullable output
+ *   d_feet_out [B][4][3]        fp32 nullable output; both NULL: CMPC_E_INVALID
+ * The outputs are computed in fp64 and rounded once: d_x_out is what cmpc_jvp_io's and
+ * cmpc_traj_jvp_io's d_x0 take at the next tick, and d_feet_out minus d_x_out's position what
+ * cmpc_traj_jvp_io's d_foot_lever takes.  An output is bit for
+ * bit the same whichever other is asked for; a NULL tangent and an array of zeros give equal
+ * results (the sign of a zero may differ).  d_feet_out of a leg that neither lands nor has a
+ * d_feet is exactly 0.  Values are treated as in cmpc_srb_vjp_io.  `size` must reach past
+ * `d_x_out`; B, the stream, allocation and capture guarantees are cmpc_srb_vjp_run's. */
+typedef struct cmpc_srb_jvp_io {
+  uint32_t size;               /* sizeof of this struct in the caller's header */
+  const double* t_now;         /* [B] required, as the other inputs */
+  const double* gait;          /* [B][6] */
+  const float* mass;           /* [B] */
+  const float* inertia_body;   /* [B][3][3] */
+  const float* force;          /* rows of 12, row stride force_stride floats */
+  int64_t force_stride;        /* >= 12 */
+  const float* hip;            /* [4][3] */
+  const float* x;              /* [B][12] the value BEFORE cmpc_srb_step; not modified */
+  const float* feet;           /* [B][4][3] likewise */
+  const uint8_t* contact_state; /* [B] likewise */
+  int32_t nsub;                /* 1 .. CMPC_SRB_GRAD_MAX_NSUB */
+  double dt;                   /* > 0, finite */
+  const float* d_x;            /* [B][12] nullable, as the next four; one required */
+  const float* d_feet;         /* [B][4][3] */
+  const float* d_force;        /* [B][12] packed */
+  const float* d_mass;         /* [B] */
+  const float* d_inertia_body; /* [B][3][3] */
+  float* d_x_out;              /* [B][12] nullable, as the next; one required */
+  float* d_feet_out;           /* [B][4][3] */
+} cmpc_srb_jvp_io;
+int cmpc_srb_jvp_run(cmpc_plan* plan, int64_t B, const cmpc_srb_jvp_io* io, void* stream);
+
 /* Measurement hooks (not on the reference's interface; used by bench.py).  A solve launches at
  * most CMPC_NUM_SOLVE_KERNELS persistent solve kernels; cmpc_plan_solve_kernel names solve
  * kernel k (0, 1 or 2) of a batch of B instances, or returns NULL if that slot is not launched:
