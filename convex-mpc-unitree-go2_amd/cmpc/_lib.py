@@ -174,6 +174,21 @@ class CSrbJvpIO(ctypes.Structure):
                               "d_feet_out")
 
 
+class CSrbIO(ctypes.Structure):
+    """cmpc_srb_io (include/cmpc.h): cmpc_srb_step's arguments (``nsub`` and ``dt`` first), then
+    the options of the force law and the wrench and the two outputs.  ``size`` is this mirror's
+    sizeof."""
+    _fields_ = ([("size", ctypes.c_uint32), ("nsub", ctypes.c_int32), ("dt", ctypes.c_double)] +
+                [(n, ctypes.c_int64 if n == "force_stride" else ctypes.c_void_p)
+                 for n in ("t_now", "gait", "mass", "inertia_body", "force", "force_stride", "hip",
+                           "x", "feet", "contact_state", "K", "x_solve", "contact", "mu", "fz_min",
+                           "wrench", "force_out", "fb_status")])
+
+
+# Plan.srb_step's options (fields of cmpc_srb_io): inputs, then outputs
+SRB_STEP_OPTIONS = ("K", "x_solve", "contact", "mu", "fz_min", "wrench", "force_out", "fb_status")
+SRB_FB_HELD, SRB_FB_APPLIED, SRB_FB_CLAMPED = 0, 1, 2  # cmpc_srb_io's fb_status values
+
 # Plan.srb_vjp's results (field g_<name> of cmpc_srb_vjp_io)
 SRB_VJP_OUTPUTS = ("x", "feet", "force", "mass", "inertia_body")
 # Plan.srb_jvp's tangents (field d_<name> of cmpc_srb_jvp_io) and results (field d_<name>_out)
@@ -238,7 +253,8 @@ def _prototypes() -> dict:
                      ("cmpc_dynamics_vjp_run", CDynamicsVjpIO),
                      ("cmpc_dynamics_jvp_run", CDynamicsJvpIO),
                      ("cmpc_traj_vjp_run", CTrajVjpIO), ("cmpc_traj_jvp_run", CTrajJvpIO),
-                     ("cmpc_srb_vjp_run", CSrbVjpIO), ("cmpc_srb_jvp_run", CSrbJvpIO)):
+                     ("cmpc_srb_vjp_run", CSrbVjpIO), ("cmpc_srb_jvp_run", CSrbJvpIO),
+                     ("cmpc_srb_step_io_run", CSrbIO)):
         table[name] = ([vp, i64, ptr(io), vp], rc)
     return table
 

@@ -57,12 +57,23 @@ class ClosedLoop:
     (``Plan.gain`` on the faces ``w`` holds) into ``self.K0``, a (B, 12, 12) float64 tensor with
     ``K0[b] = d U[:, 0] / d x0``: between two MPC ticks ``U[:, 0] + K0 (x - x_solve)`` is the
     first-order correction of the held forces.  It runs on the tick's stream too and keeps
-    ``self.x_solve`` as ``report`` does."""
+    ``self.x_solve`` as ``report`` does.
+
+    ``feedback=True`` (implies ``gain``): the plant applies that correction at every substep
+    (``Plan.srb_step`` with ``K0``, ``x_solve``, the contact table and the loop's ``mu`` /
+    ``fz_min``), each leg the MPC planned in stance kept inside its friction pyramid;
+    ``self.fb_status`` (B,) uint8 says per robot whether the law was held (0: ``K0`` not finite,
+    ``mu`` / ``fz_min`` invalid), applied (1) or applied and clamped (2).
+
+    ``push=True``: ``self.wrench``, a (B, 6) fp32 tensor of zeros, is the external wrench on every
+    robot (world force at the COM, world torque about it).  Written in place, it takes effect at
+    the next tick, a replay of the captured graph included, and is held until rewritten."""
 
     def __init__(self, B: int, plan: Optional[Plan] = None, gait_hz: float = synth.GAIT_HZ,
                  duty: float = synth.GAIT_DUTY, offsets=synth.TROT_OFFSETS, nsub: int = 20,
                  seed: int = 0, device="cuda", shift_warm: bool = True, mu=None, fz_min=None,
-                 Q=None, R=None, report: bool = False, gain: bool = False):
+                 Q=None, R=None, report: bool = False, gain: bool = False,
+                 feedback: bool = False, push: bool = False):
         self.plan = plan or Plan(SolverParams(max_batch=B))
         self.B, self.N = B, self.plan.params.N
         dev = torch.device(device)
@@ -116,13 +127,23 @@ class ClosedLoop:
             torch.as_tensor(v, dtype=f32).expand(B, 12).contiguous().to(dev, copy=True)
             for v in (Q, R))
         self.report = bool(report)
-        self.gain = bool(gain)
+        self.feedback = bool(feedback)
+        self.gain = bool(gain) or self.feedback
         if self.report or self.gain:
             self.x_solve = torch.empty_like(self.x)
         if self.report:
             self.kkt = torch.empty((B, 4), dtype=f64, device=dev)
         if self.gain:
             self.K0 = torch.empty((B, 12, 12), dtype=f64, device=dev)
+        # the plant's options (Plan.srb_step): none by default, so the tick is cmpc_srb_step's
+        self.plant = {}
+        if self.feedback:
+            self.fb_status = torch.zeros((B,), dtype=torch.uint8, device=dev)
+            self.plant.update(K=self.K0, x_solve=self.x_solve, contact=self.ct, mu=self.mu,
+                              fz_min=self.fz_min, fb_status=self.fb_status)
+        if push:
+            self.wrench = torch.zeros((B, 6), dtype=f32, device=dev)
+            self.plant.update(wrench=self.wrench)
         self.shift_warm = shift_warm
         self.warm = False
         self.graph = None
@@ -169,7 +190,8 @@ class ClosedLoop:
                    stream=stream)
         # the plant reads U[:, 0] off the rows of w (test_MPC.py:196)
         p.srb_step(self.t, self.gait, self.mass, self.I_body, self.w[:, 12 * N:], self.hip, self.x,
-                   self.feet, self.contact, self.nsub, self.dt / self.nsub, stream=stream)
+                   self.feet, self.contact, self.nsub, self.dt / self.nsub, stream=stream,
+                   **self.plant)
         self.t.add_(self.dt)
 
     def tick(self):

@@ -177,6 +177,15 @@ def _srb_spec(B) -> tuple:
 
 
 @_spec
+def _srb_io_spec(B, N) -> dict:
+    """The options of cmpc_srb_step_io_run (cmpc_srb_io's fields after contact_state)."""
+    f32, u8 = torch.float32, torch.uint8
+    return dict(K=(torch.float64, (B, 12, 12)), x_solve=(f32, (B, 12)), contact=(u8, (B, 4, N)),
+                mu=(f32, (B,)), fz_min=(f32, (B,)), wrench=(f32, (B, 6)),
+                force_out=(f32, (B, 12)), fb_status=(u8, (B,)))
+
+
+@_spec
 def _srb_grad_spec(B) -> tuple:
     """(inputs, gradients in, gradients out, tangents in, tangents out) of cmpc_srb_vjp_run and
     cmpc_srb_jvp_run, ``force`` apart (_force_rows); the two results are name -> (io field, dtype,
@@ -846,13 +855,37 @@ class Plan:
                                    tau_max, p[12]))[0]
 
     def srb_step(self, t_now, gait, mass, inertia_body, force, hip, x, feet, contact_state, nsub,
-                 dt, stream=None):
+                 dt, stream=None, K=None, x_solve=None, contact=None, mu=None, fz_min=None,
+                 wrench=None, force_out=None, fb_status=None):
         """``nsub`` substeps of ``dt`` of the single-rigid-body plant for B robots
         (cmpc_srb_step, include/cmpc.h).  t_now (B,) and gait (B, 6) fp64; mass (B,),
         inertia_body (B, 3, 3) and hip (4, 3) fp32; ``force`` as for :meth:`leg_torque`; x
-        (B, 12) fp32, feet (B, 4, 3) fp32 and contact_state (B,) uint8 are updated in place."""
+        (B, 12) fp32, feet (B, 4, 3) fp32 and contact_state (B,) uint8 are updated in place.
+
+        With any of the options the step is cmpc_srb_step_io_run's (include/cmpc.h).  ``K``
+        (B, 12, 12) float64, :meth:`gain`'s ``K``, with ``x_solve`` (B, 12) fp32, the state the
+        forces were solved from, and ``contact`` (B, 4, N) uint8, the solve's contact table: every
+        substep applies ``force + K (x - x_solve)``, the legs the MPC planned in stance clamped to
+        ``fz >= fz_min`` and ``|fx|, |fy| <= mu fz`` (``mu`` / ``fz_min``: (B,) fp32, None: the
+        plan's constants).  A robot whose ``K`` is not finite or whose ``mu`` / ``fz_min`` is
+        invalid holds ``force``.  ``wrench`` (B, 6) fp32: a world force at the COM and a world
+        torque about it, held over the substeps.  ``force_out`` (B, 12) fp32 receives the forces
+        of the last substep and ``fb_status`` (B,) uint8 0 (held), 1 (law applied) or 2 (applied
+        and clamped)."""
         B = x.shape[0]
         _force_rows(force, B, self.device)
+        options = dict(K=K, x_solve=x_solve, contact=contact, mu=mu, fz_min=fz_min, wrench=wrench,
+                       force_out=force_out, fb_status=fb_status)
+        if any(t is not None for t in options.values()):
+            self._need("cmpc_srb_step_io_run", "srb_step")
+            if K is not None and (x_solve is None or contact is None):
+                raise ValueError("srb_step: K needs x_solve and contact")
+            io = _lib.CSrbIO()
+            self._srb_grad_io(io, _srb_spec(B)[0], t_now, gait, mass, inertia_body, force, hip, x,
+                              feet, contact_state, nsub, dt)
+            self._fill_io(io, _srb_io_spec(B, self.params.N), {}, options)
+            self._run_io("cmpc_srb_step_io_run", io, B, stream)
+            return
         self._pipeline(
             "cmpc_srb_step", _srb_spec(B),
             (t_now, gait, mass, inertia_body, hip, x, feet, contact_state), None, stream,

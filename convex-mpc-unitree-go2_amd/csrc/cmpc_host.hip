@@ -27,6 +27,7 @@
 #include "cmpc_dynamics_grad.hip"  // reverse- and forward-mode derivatives of the dynamics builder
 #include "cmpc_traj_grad.hip"      // reverse- and forward-mode derivatives of the trajectory generator
 #include "cmpc_sim_grad.hip"       // reverse- and forward-mode derivatives of the rigid-body plant
+#include "cmpc_sim_fb.hip"         // the plant with the first-order force law and an external wrench
 
 constexpr int kNumGroups = 3;  // solve kernels (register classes), see solve_group_kernel
 static_assert(kNumGroups == CMPC_NUM_SOLVE_KERNELS, "one timing slot per solve kernel");
@@ -957,6 +958,38 @@ int cmpc_srb_jvp_run(cmpc_plan* pl, int64_t B, const cmpc_srb_jvp_io* io, void* 
                            a.d_x_out, a.d_feet_out};
   return launch(cmpc::srb_jvp_kernel, "srb_jvp_kernel launch", (unsigned)((B + 63) / 64), 64, 0,
                 stream, B, (int)a.nsub, a.dt, k);
+}
+
+int cmpc_srb_step_io_run(cmpc_plan* pl, int64_t B, const cmpc_srb_io* io, void* stream) {
+  const char* what = "cmpc_srb_step_io_run";
+  const std::string w(what);
+  cmpc_srb_io a;
+  if (int rc = io_copy(io, offsetof(cmpc_srb_io, contact_state) + sizeof(io->contact_state), what,
+                       "cmpc_srb_io", a))
+    return rc;
+  if (int rc = check_pipeline(pl, what, B < 0 || a.nsub < 0, ": negative batch or nsub")) return rc;
+  if (!(a.dt > 0.0) || !std::isfinite(a.dt)) return fail(CMPC_E_INVALID, w + ": dt must be > 0");
+  if (a.force_stride < 12) return fail(CMPC_E_INVALID, w + ": force_stride must be >= 12");
+  if (B == 0 || a.nsub == 0) return CMPC_OK;
+  if (!a.t_now || !a.gait || !a.mass || !a.inertia_body || !a.force || !a.hip || !a.x || !a.feet ||
+      !a.contact_state)
+    return fail(CMPC_E_INVALID, w + ": null array argument");
+  if (a.K && (!a.x_solve || !a.contact))
+    return fail(CMPC_E_INVALID, w + ": K needs x_solve and contact");
+  if ((uintptr_t)a.K % 16) return fail(CMPC_E_INVALID, w + ": K must be 16-byte aligned");
+  const unsigned blocks = (unsigned)((B + 255) / 256);
+  if (!a.K && !a.wrench && !a.force_out && !a.fb_status)  // the plain plant, bit for bit
+    return launch(cmpc::srb_kernel, "srb_kernel launch", blocks, 256, 0, stream, B, (int)a.nsub,
+                  a.dt, a.t_now, a.gait, a.mass, a.inertia_body, a.force, a.force_stride, a.hip,
+                  a.x, a.feet, a.contact_state);
+  const cmpc::SrbFbArgs k{a.t_now, a.gait, a.mass, a.inertia_body, a.force, a.force_stride, a.hip,
+                          a.x, a.feet, a.contact_state, a.K, a.x_solve, a.contact, a.mu, a.fz_min,
+                          pl->kp.mu, pl->kp.fz_min, pl->kp.N, a.wrench, a.force_out, a.fb_status};
+  // one thread per robot, one wave per block; with K the block stages its robots' gains in LDS
+  const auto kernel = a.K ? cmpc::srb_feedback_kernel<true> : cmpc::srb_feedback_kernel<false>;
+  return launch(kernel, "srb_feedback_kernel launch",
+                (unsigned)((B + cmpc::kSrbFbRobots - 1) / cmpc::kSrbFbRobots), cmpc::kSrbFbRobots,
+                0, stream, B, (int)a.nsub, a.dt, k);
 }
 
 int cmpc_plan_set_timing(cmpc_plan* pl, int enable) {

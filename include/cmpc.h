@@ -865,6 +865,68 @@ int cmpc_srb_step(cmpc_plan* plan, int64_t B, int nsub, double dt, const double*
                   const float* force, int64_t force_stride, const float* hip, float* x,
                   float* feet, uint8_t* contact_state, void* stream);
 
+/* cmpc_srb_step with two options: the first-order MPC force law applied at every substep, and an
+ * external wrench.  With neither, and no output asked for, it is cmpc_srb_step bit
+ * for bit.  The substep is cmpc_srb_step's with two additions.
+ *
+ * Force law.  With x_s the fp32 state at a substep's start, a robot that has the law applies
+ *   delta = x_s - x_solve                     in fp32, widened to fp64
+ *   u_i   = fl32(U0_i + sum_j K_ij delta_j)    in fp64, j = 0 .. 11 in that order, U0 first
+ * and, for each leg l with contact[b][l][0] != 0 (the MPC's stance at step 0),
+ *   fz = max(u_z, fz_min),  fx = min(max(u_x, -mu fz), mu fz),  fy likewise (the clamped fz).
+ * A leg with contact[b][l][0] == 0 keeps its U0 triple: no feedback, no clamp, so a leg the MPC
+ * planned in swing never receives fz_min.  Which legs apply their force is still decided by the
+ * gait at the substep time, as in cmpc_srb_step.
+ * A robot holds U0 for the whole call and gets fb_status 0 when K is NULL, when its K block has
+ * an entry that is not finite (cmpc_gain_run writes NaN for an inconsistent face mask), or when
+ * its mu or fz_min is invalid by cmpc_solve_io's rules (mu not finite or <= 0, fz_min not
+ * finite).  fb_status 1: the law was applied; 2: and at least one clamp changed a component of a
+ * force that a leg in stance by the gait applied, in at least one substep.  force_out receives
+ * the 12 forces of the last substep before the gait gates them (a held robot's: U0).
+ *
+ * Wrench.  wrench[b][0:3] is added to the force sum F and wrench[b][3:6] to the torque sum T of
+ * every substep, whatever the contacts: a world force at the COM and a world torque about it.
+ *
+ *   nsub .. contact_state   as for cmpc_srb_step, with its checks
+ *   K        [B][12][12] fp64, cmpc_gain_run's K; 16-byte aligned; needs x_solve and contact
+ *            (else CMPC_E_INVALID)
+ *   x_solve  [B][12]  the state the forces were solved from
+ *   contact  [B][4][N] the solve's contact table, N the plan's
+ *   mu, fz_min [B], NULL: the plan's constants
+ * Neither the solve's status nor friction at the feet enters; there is no derivative entry for
+ * the options (cmpc_srb_vjp_run and cmpc_srb_jvp_run differentiate the hold-force plant).
+ * `size` is the caller's sizeof of the struct (fields past it read as NULL or 0); it must reach
+ * past `contact_state`.  B >= 0 (B == 0 or nsub == 0 returns CMPC_OK with nothing written); no
+ * workspace is used, so the plan's max_batch does not limit B; rows past B are untouched.  Every
+ * sum runs in one thread in a fixed order: the results are bitwise repeatable and do not depend on
+ * B or on the robot's row.  Asynchronous on `stream`, no allocation, no host synchronisation,
+ * graph-capturable; the plan's device must be current. */
+typedef struct cmpc_srb_io {
+  uint32_t size;               /* sizeof of this struct in the caller's header */
+  int32_t nsub;                /* as cmpc_srb_step's, as the fields down to contact_state */
+  double dt;
+  const double* t_now;         /* [B] */
+  const double* gait;          /* [B][6] */
+  const float* mass;           /* [B] */
+  const float* inertia_body;   /* [B][3][3] */
+  const float* force;          /* rows of 12, row stride force_stride floats */
+  int64_t force_stride;        /* >= 12 */
+  const float* hip;            /* [4][3] */
+  float* x;                    /* [B][12] in/out */
+  float* feet;                 /* [B][4][3] in/out */
+  uint8_t* contact_state;      /* [B] in/out */
+  /* options, all nullable */
+  const double* K;             /* [B][12][12] fp64: cmpc_gain_run's K */
+  const float* x_solve;        /* [B][12]: the state the forces were solved from */
+  const uint8_t* contact;      /* [B][4][N]: the solve's contact table (N the plan's) */
+  const float* mu;             /* [B]; NULL: the plan's constant */
+  const float* fz_min;         /* [B]; NULL: the plan's constant */
+  const float* wrench;         /* [B][6]: world force at the COM, world torque about it */
+  float* force_out;            /* [B][12] out: the law's forces at the last substep */
+  uint8_t* fb_status;          /* [B] out: 0 held, 1 law applied, 2 law applied and clamped */
+} cmpc_srb_io;
+int cmpc_srb_step_io_run(cmpc_plan* plan, int64_t B, const cmpc_srb_io* io, void* stream);
+
 /* Gradients of a loss through cmpc_srb_step, on the device: from dL/dx' and dL/dfeet' to the
  * gradients in the state, the feet, the held forces, the mass and the body inertia.  The function
  * differentiated is the plant's documented model evaluated in fp64 on the fp32
